@@ -1,6 +1,6 @@
 """bench.py -- CT volumes/sec of the Med3D + dRAM train step on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0|1|2|3|4|5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0|1|2|3|4|5] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = forward + loss + backward + (N>1: RCCL gradient all-reduce, SyncBN exchanges) +
@@ -8,7 +8,11 @@ fused Adam update on one batch of synthetic volumes already resident in HBM
 (SURVEY.md §8d recipe).  Default workload = BASELINE.json configs[1]:
 conf/med3d18.yaml (resnet18segcls), batch 2 per GPU, 1x128x256x256, fp32.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+A plain run sets up, warms up, times K steps and prints ONE JSON line (rank 0): metric, value (volumes/s), unit,
+higher_is_better, dtype, ms_per_step (wall clock of one timed step) and how the step was timed.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB; seeded samples
+of the larger arrays): loss, the forward's dense volumes and scores, and the updated parameters, their gradients
+and the BN buffers.  --full adds the measurements that take runs of their own:
   roofline     -- the kernel family with the largest time share ON THE CONFIG RUN, from the library's own
                   kernel timeline (hipEvent pairs around every kernel launch, on the launch stream, over the
                   same K steps run a second time right after the timed region -- the ~1,400 event records per
@@ -21,6 +25,8 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
   cpu_baseline -- the CPU oracle (oracle/med3d_oracle.py, torch CPU ops): 1 warm-up + 2 timed train steps
                   of one volume of the same shape, host threads stated (N=1, rank 0 only; runs BEFORE the
                   GPU section)
+  data parallel -- collectives_per_step, plain_ms_per_step / exposed_collective_ms (the same K steps once more
+                  without the collectives) and stat_exchange_ms_bracketed
 """
 import argparse
 import json
@@ -117,7 +123,17 @@ def synth_batch(B, dims, rank, device):
     return image, lung, em, cle, pse
 
 
-def make_step(factory, module, opt, batch):
+def stash_outputs(stash, dense, outs):
+    """Keep the forward's outputs of the latest step in `stash` (--dump-outputs only: a plain run holds no extra tensors).
+    Detached: the outputs themselves would keep the step's autograd graph, and with it the parameters' AccumulateGrad
+    nodes, alive into the next step -- into GraphedTrainStep's side-stream warm-up and capture, where torch then finds
+    those nodes bound to the default stream and the capture breaks."""
+    if stash is not None:
+        stash.update(dense_cle=dense[0].detach(), dense_pse=dense[1].detach(), out_cle=outs[0].detach(),
+                     out_pse=outs[1].detach())
+
+
+def make_step(factory, module, opt, batch, stash=None):
     from bodyct_dram_emph_subtype_amd.models import cls_train_loss, reg_train_loss
     image, lung, em, cle, pse = batch
     if factory.endswith("cls"):
@@ -126,7 +142,8 @@ def make_step(factory, module, opt, batch):
 
         def step():
             opt.zero_grad(set_to_none=True)
-            _, outs = module(image, lung)
+            dense, outs = module(image, lung)
+            stash_outputs(stash, dense, outs)
             loss, _ = cls_train_loss(outs, cle, pse, cw, pw)     # models.py:253-258 (K16: torch glue)
             loss.backward()
             opt.step()
@@ -139,6 +156,7 @@ def make_step(factory, module, opt, batch):
     def step():
         opt.zero_grad(set_to_none=True)
         dense, outs = module(image, lung)
+        stash_outputs(stash, dense, outs)
         loss, _ = reg_train_loss(dense, outs, lung, em, cle, pse, cwt, pwt)
         loss.backward()
         opt.step()
@@ -266,6 +284,68 @@ def family_table(fams, steps, step_s, bf16_mfma=("conv_bf16", "wgrad_bf16")):
     return rows
 
 
+DUMP_SAMPLE = 1 << 21          # elements kept of a larger output array (a fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _host_array(t, seed=0):
+    """Tensor -> float32 numpy array on the host; above DUMP_SAMPLE elements, the elements at a fixed, seeded set of
+    flat indices (the same indices for every array of the same size: parameters and their gradients line up)."""
+    t = t.detach()
+    n = t.numel()
+    if n > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def snapshot_outputs(module, loss, stash, train=True):
+    """What the last timed step computed, copied to the host right after the timed region (anything that runs later
+    moves the model on): the loss, the forward's dense volumes and scores (`stash`), and the step's result for the
+    caller's model -- the updated parameters, their gradients and the BN buffers, each flattened in named order.
+    The predict path (train=False): the mean of the pasted CLE volume it returns and its per-scan outputs (`stash`)."""
+    named = {("loss" if train else "mean_full_cle"): loss.detach().reshape(1)}
+    named.update((k, torch.as_tensor(v)) for k, v in stash.items())
+    if not train:
+        return {k: _host_array(v) for k, v in named.items()}
+    params = [p for _, p in module.named_parameters()]
+    named["params"] = torch.cat([p.detach().reshape(-1) for p in params])
+    named["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                for p in params])
+    bufs = [b.detach().reshape(-1).float() for _, b in module.named_buffers() if b.is_floating_point()]
+    if bufs:
+        named["buffers"] = torch.cat(bufs)
+    return {k: _host_array(v) for k, v in named.items()}
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total / 2**20:.1f} MB of outputs exceeds {DUMP_MAX_BYTES >> 20} MB")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
+def load_native():
+    """Load libdram_hip.so.  A process that may write to the build directory goes through the package's own load, which
+    rebuilds first when the sources changed.  One that may not -- the tree was built by another user, or is read-only --
+    loads the library build() left there (a package without the read-only check would otherwise fail on the build lock);
+    _lib.load still refuses a library built from another include/dram_hip.h."""
+    from bodyct_dram_emph_subtype_amd import _build, _lib
+    path = os.path.join(_build.BUILD, ".lock")
+    while not os.path.exists(path):
+        path = os.path.dirname(path)
+    if os.access(path, os.W_OK):
+        return _lib.load()
+    if hasattr(_build, "is_current") and not _build.is_current():
+        raise RuntimeError(f"{_build.LIB_PATH} is older than the sources and this process may not rebuild it: "
+                           "run __graft_entry__.build()")
+    return _lib.load(build=False)
+
+
 def self_launch(n: int) -> int:
     """Run this same command line under `python -m torch.distributed.run --nproc-per-node n` as a child
     process (one rank per GPU, rendezvous on 127.0.0.1 at a free port), relay its stdout / stderr, return its
@@ -301,17 +381,22 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline, the kernel timeline (roofline table; "
+                         "--timeline defaults to 'after') and, data parallel, the step without its collectives")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) leave out the CPU baseline")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--dtype", choices=("f32", "bf16"), default=None,
                     help="storage type of the activations: f32 = the reference's default arithmetic; bf16 = its "
                          "`--precision bf16` (bf16 activations, fp32 accumulation / statistics / parameters).  Default: "
                          "what BASELINE.json names for the config (bf16 for configs 2 and 4, f32 otherwise)")
     ap.add_argument("--detail", type=str, default="", help="write a per-convolution-call timing table to this file")
-    ap.add_argument("--timeline", choices=("after", "in", "off"), default="after",
+    ap.add_argument("--timeline", choices=("after", "in", "off"), default=None,
                     help="kernel timeline (roofline table): 'after' = a second pass of the same K steps right after "
-                         "the timed region (default: the ~1,400 hipEventRecords per step cost 4-5 %% of a step, "
-                         "so `value` is timed without them); 'in' = inside the timed region; 'off' = none")
+                         "the timed region (default with --full: the ~1,400 hipEventRecords per step cost 4-5 %% of a step, "
+                         "so `value` is timed without them); 'in' = inside the timed region; 'off' = none (default)")
     ap.add_argument("--predict", action="store_true",
                     help="time the predict path instead (models.py:430-450 + processor.py:111-129: eval forward, dRAM "
                          "up-projection x ess mask, percentages, resample + paste to an original grid) -- an extra "
@@ -332,6 +417,10 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="keep the data-parallel collectives (RCCL) in place at world size 1")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.timeline is None:
+        args.timeline = "after" if args.full else "off"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N` (the reference's `--ngpus N` alone starts N ranks, train.py:24,100-104):
@@ -357,7 +446,7 @@ def main():
         args.dtype = "bf16" if args.config in BF16_CONFIGS else "f32"
 
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(factory, dims, B)          # first: the GPU burst below is then the tail of the run
 
     if args.share_gpu:
@@ -396,10 +485,9 @@ def main():
         else:
             dist.init_process_group("gloo", rank=rank, world_size=world)
 
-    import bodyct_dram_emph_subtype_amd as dram
     from bodyct_dram_emph_subtype_amd import med3d, ops
     from bodyct_dram_emph_subtype_amd.optim import FusedAdam
-    dram.load_library()
+    load_native()
 
     torch.manual_seed(0)
     kw = dict(n_classes=[6, 3]) if factory.endswith("cls") else {}
@@ -414,8 +502,10 @@ def main():
         dctx = ddist.attach(module, force=args.force_dist)
     opt = FusedAdam(module.parameters(), lr=args.lr, capturable=bool(args.graph))
     batch = synth_batch(B, dims, rank, device)
-    step = make_step(factory, module, opt, batch)
+    stash = {} if args.dump_outputs else None
+    step = make_step(factory, module, opt, batch, stash)
     graph_choice = None
+    graph_warmup = 2                         # eager steps GraphedTrainStep runs before its capture
     if args.graph == "auto":
         for _ in range(3):                   # plans, workspaces, optimizer state, allocator pool
             step()
@@ -435,6 +525,11 @@ def main():
             args.graph = bool(int(flag.item()))
         graph_choice = (f"auto: the host issued {nprobe} untimed eager steps in {issue_s / nprobe * 1e3:.1f} ms/step of "
                         f"{total_s / nprobe * 1e3:.1f} ms/step -> " + ("hipGraph replay" if args.graph else "eager two-stream step"))
+        if not args.graph:
+            # as many untimed updates as the capture's warm-up: the timed steps then start from the same model and
+            # optimizer state whichever form the probe picked (--dump-outputs of two runs compare output for output)
+            for _ in range(graph_warmup):
+                step()
     if args.predict:
         from bodyct_dram_emph_subtype_amd import models as dmodels, processor
         if not factory.endswith("reg"):
@@ -451,6 +546,11 @@ def main():
         def step():
             out = lm.predict_step(pb, 0)
             res = processor.build_outputs([out], want_u8=True)
+            if stash is not None:
+                for b, r in enumerate(res):
+                    stash[f"full_cle_{b}"], stash[f"full_pse_{b}"] = r["full_cle"], r["full_pse"]
+                    stash[f"metrics_{b}"] = torch.tensor([float(v) for _, v in sorted(r["metrics"].items())],
+                                                         dtype=torch.float64)
             return res[0]["full_cle"].float().mean()
         args.timeline = "off"
     if args.graph and dctx is not None and not dctx.capturable:
@@ -464,17 +564,21 @@ def main():
             pw = torch.full((3,), 1.0 / 3, device=device)
 
             def loss_fn(image, lung, em, cle, pse):
-                return cls_train_loss(module(image, lung)[1], cle, pse, cw, pw)[0]
+                dense, outs = module(image, lung)
+                stash_outputs(stash, dense, outs)      # (captured: the replays rewrite these tensors in place)
+                del dense                              # (the cls loss does not read the volumes: released here)
+                return cls_train_loss(outs, cle, pse, cw, pw)[0]
         else:
             cwt = torch.full((B,), 1.0 / 6, device=device)
             pwt = torch.full((B,), 1.0 / 3, device=device)
 
             def loss_fn(image, lung, em, cle, pse):
                 dense, outs = module(image, lung)
+                stash_outputs(stash, dense, outs)
                 return reg_train_loss(dense, outs, lung, em, cle, pse, cwt, pwt)[0]
         eager_step = step
         try:
-            graphed = GraphedTrainStep(module, opt, loss_fn, batch, warmup=2, streams=args.graph_streams)
+            graphed = GraphedTrainStep(module, opt, loss_fn, batch, warmup=graph_warmup, streams=args.graph_streams)
             if graphed.graph is None:           # (data parallel: the runtime refused to record the collectives)
                 args.graph = False
             else:
@@ -524,13 +628,16 @@ def main():
     ops.set_profiler(None)
     if args.detail:
         single_stream(False)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = snapshot_outputs(module, loss, stash, train=not args.predict)
     tl_step_s = dt / args.steps
-    # Data parallel: what do the collectives COST a step?  The same K steps once more WITHOUT them (context detached,
-    # every rank on its own; same eager / graph form) right after the timed region: exposed_collective_ms = the
+    # Data parallel (--full): what do the collectives COST a step?  The same K steps once more WITHOUT them (context
+    # detached, every rank on its own; same eager / graph form) right after the timed region: exposed_collective_ms = the
     # difference of the two step times, which by construction reconciles with the wall clock (the event-bracketed
     # sum of round 4 saw neither the cross-stream hand-offs nor RCCL's own launch overhead).
     plain_step_ms = None
-    if dctx is not None and not args.predict:
+    if args.full and dctx is not None and not args.predict:
         module._dist = None
         try:
             pstep = eager_step if args.graph else step
@@ -550,9 +657,10 @@ def main():
     if args.graph:
         step = eager_step                   # the timeline pass brackets individual launches: eager
     # every rank runs the second pass (its steps contain collectives); rank 0 records the timeline
-    if args.timeline == "after" or (dctx is not None and args.timeline == "off"):
-        # (data parallel with --timeline off: the second pass still runs, without the kernel timeline, so that EVERY N > 1
-        # line carries exposed_collective_ms)
+    second_pass = args.timeline == "after" or (args.full and dctx is not None and args.timeline == "off")
+    if second_pass:
+        # (data parallel with --full --timeline off: the second pass still runs, without the kernel timeline, so that EVERY
+        # such N > 1 line carries exposed_collective_ms)
         # same K steps again, every kernel launch bracketed by hipEvents on its launch stream.  The timeline pass
         # runs the step on ONE stream (DRAM_WGRAD_STREAM=0): with the weight-gradient kernels overlapping the
         # data-gradient chain on a second stream a kernel's event interval would also contain the time it
@@ -619,9 +727,9 @@ def main():
             "peak_hbm_gb": torch.cuda.max_memory_allocated(device) / 1e9,
         }
         if dctx is not None:
-            if args.timeline in ("after", "off"):    # counted over the eager second pass (a replayed graph issues none from the host)
+            if second_pass:                          # counted over the eager second pass (a replayed graph issues none from the host)
                 out["collectives_per_step"] = {k: (v - stats0[k]) / (args.steps + 1) for k, v in dctx.stats.items()}
-            else:
+            elif args.timeline == "in":
                 out["collectives_per_step"] = {k: v / (args.warmup + args.steps) for k, v in dctx.stats.items()}
             out["collective_transport"] = "rccl-c-api" if dctx._stat is not None else f"torch.distributed/{args.backend}"
             if plain_step_ms is not None:
@@ -629,7 +737,7 @@ def main():
                 # right after the timed region; on rank 0 -- dt is the max over ranks)
                 out["plain_ms_per_step"] = plain_step_ms
                 out["exposed_collective_ms"] = 1e3 * step_s - plain_step_ms
-            if args.timeline in ("after", "off"):
+            if second_pass:
                 # event pairs around every SyncBN statistic exchange on the data path's stream, per step (single-stream
                 # pass; the gradient buckets are asynchronous and not part of it): a LOWER bound of the above
                 out["stat_exchange_ms_bracketed"] = exposed_ms
@@ -684,6 +792,8 @@ def main():
             }
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if use_dist:

@@ -72,10 +72,40 @@ def have_hipcc() -> bool:
         return False
 
 
+def _plan():
+    """(flags, [(source, object, key), ...], link key): the key of an object is the sha1 of its source + every
+    header + the flags, the library's is the sha1 of the object keys."""
+    flags = _flags()
+    hdrs = b"".join(_read(os.path.join(d, f)) for d in (INCLUDE, CSRC) for f in sorted(os.listdir(d))
+                    if f.endswith(".h"))
+    objs = []
+    for src in _sources():
+        s = os.path.join(CSRC, src)
+        key = hashlib.sha1(_read(s) + hdrs + " ".join(flags).encode()).hexdigest()
+        objs.append((s, os.path.join(BUILD, src[:-4] + ".o"), key))
+    return flags, objs, hashlib.sha1("".join(k for _, _, k in objs).encode()).hexdigest()
+
+
+def _stored_key(path: str) -> str:
+    kf = path + ".key"
+    return _read(kf).decode() if os.path.exists(kf) else ""
+
+
+def is_current() -> bool:
+    """Every object and the library carry the keys of the present sources and flags.  Reads only."""
+    _, objs, link_key = _plan()
+    return (all(os.path.exists(o) and _stored_key(o) == key for _, o, key in objs)
+            and os.path.exists(LIB_PATH) and _stored_key(LIB_PATH) == link_key)
+
+
 def build_library(force: bool = False, verbose: bool = False) -> str:
     """Incremental by CONTENT (not mtime: the tree is copied to the GPU box): an object is
     rebuilt when the sha1 of its source + every header + the flags differs from the key
-    stored beside it, the library is relinked when any object key changed."""
+    stored beside it, the library is relinked when any object key changed.  A library that is
+    current is returned without writing anything (no lock either): a process that may not write
+    to the tree -- another user than the one who built it, a read-only checkout -- still loads it."""
+    if not force and is_current():
+        return LIB_PATH
     os.makedirs(BUILD, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
     import fcntl
@@ -86,20 +116,12 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 
 def _build_locked(force: bool, verbose: bool) -> str:
     hipcc = _hipcc()
-    flags = _flags()
-    hdrs = b"".join(_read(os.path.join(d, f)) for d in (INCLUDE, CSRC) for f in sorted(os.listdir(d))
-                    if f.endswith(".h"))
-    jobs, objs, keys = [], [], []
-    for src in _sources():
-        s = os.path.join(CSRC, src)
-        o = os.path.join(BUILD, src[:-4] + ".o")
-        key = hashlib.sha1(_read(s) + hdrs + " ".join(flags).encode()).hexdigest()
-        kf = o + ".key"
+    flags, plan, link_key = _plan()
+    jobs, objs = [], []
+    for s, o, key in plan:
         objs.append(o)
-        keys.append(key)
-        old = _read(kf).decode() if os.path.exists(kf) else ""
-        if force or not os.path.exists(o) or old != key:
-            jobs.append((key, kf, [hipcc] + flags + ["-c", s, "-o", o]))
+        if force or not os.path.exists(o) or _stored_key(o) != key:
+            jobs.append((key, o + ".key", [hipcc] + flags + ["-c", s, "-o", o]))
 
     def run(cmd):
         if verbose:
@@ -119,10 +141,8 @@ def _build_locked(force: bool, verbose: bool) -> str:
     if jobs:
         with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
             list(ex.map(compile_one, jobs))
-    link_key = hashlib.sha1("".join(keys).encode()).hexdigest()
     lk = LIB_PATH + ".key"
-    old = _read(lk).decode() if os.path.exists(lk) else ""
-    if force or bool(jobs) or not os.path.exists(LIB_PATH) or old != link_key:
+    if force or bool(jobs) or not os.path.exists(LIB_PATH) or _stored_key(LIB_PATH) != link_key:
         if os.path.exists(lk):
             os.remove(lk)
         run([hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB_PATH] + objs)

@@ -314,7 +314,7 @@ def test_bench_gpus2_self_launches_its_ranks():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "0",
-           "--backend", "gloo", "--share-gpu", "--timeline", "off"]
+           "--backend", "gloo", "--share-gpu", "--timeline", "off", "--full"]
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd="/tmp")
     try:
         out, err = proc.communicate(timeout=420)
@@ -342,7 +342,7 @@ def test_bench_line_is_alone_on_stdout_with_rccl_up():
         sk.bind(("127.0.0.1", 0))
         env["MASTER_PORT"] = str(sk.getsockname()[1])
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "0", "--steps", "2", "--warmup", "1", "--force-dist",
-           "--no-cpu-baseline", "--timeline", "off"]
+           "--no-cpu-baseline", "--timeline", "off", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
@@ -383,13 +383,40 @@ def test_default_bench_line_says_how_the_step_was_timed():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         env = dict(env, MASTER_PORT=str(sk.getsockname()[1]))
-    r = subprocess.run(base + ["--force-dist"], env=env, capture_output=True, text=True, timeout=420, cwd="/tmp")
+    r = subprocess.run(base + ["--force-dist", "--full"], env=env, capture_output=True, text=True, timeout=420, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads(r.stdout.splitlines()[0])
     cfg = rec["config"]
     assert rec["collective_transport"] == "rccl-c-api" and rec["plain_ms_per_step"] > 0
     assert cfg["graph_choice"].startswith("auto: the host issued 4 untimed eager steps")
     assert cfg["graph_choice"].endswith("hipGraph replay" if cfg["hip_graph"] else "eager two-stream step")
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_last_step():
+    """A plain `python bench.py` measures the headline only (the CPU baseline and the roofline pass come with --full), and
+    --dump-outputs DIR writes what the last timed step computed: float32 .npy files, <= 64 MB, whose loss is the line's."""
+    import json
+    import subprocess
+    import tempfile
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    with tempfile.TemporaryDirectory() as d:
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "0", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", d]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd="/tmp")
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.splitlines()
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert "cpu_baseline" not in rec and "roofline" not in rec
+        assert rec["steps"] == 3 and rec["unit"] == "volumes/sec" and rec["higher_is_better"] is True
+        assert abs(rec["value"] - 1e3 / rec["ms_per_step"]) < 1e-6 * rec["value"]        # config 0: batch 1
+        arrays = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert {"loss", "dense_cle", "dense_pse", "out_cle", "out_pse", "params", "grads", "buffers"} <= set(arrays)
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["out_cle"].shape == (1, 6) and arrays["out_pse"].shape == (1, 3)
+    assert abs(float(arrays["loss"][0]) - rec["loss"]) <= 1e-6 * max(1.0, abs(rec["loss"]))
+    assert np.isfinite(arrays["grads"]).all() and np.abs(arrays["grads"]).max() > 0
 
 
 def test_two_rank_bf16_storage_matches_ddp_syncbn_emulation():

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/dp; mkdir -p $O
 cd $R
 for spec in "1 f32" "2 bf16" "3 bf16"; do
   set -- $spec
-  python bench.py --config $1 --dtype $2 --force-dist --steps 20 --warmup 5 --no-cpu-baseline --timeline off \
+  python bench.py --full --config $1 --dtype $2 --force-dist --steps 20 --warmup 5 --no-cpu-baseline --timeline off \
       > $O/fd_c$1_$2.json 2> $O/fd_c$1_$2.err || echo "config $1 $2: rc=$?" >> $O/failures.txt
 done
 if [ "$1" != "" ] && [ "${DP_AB:-0}" = "1" ]; then
@@ -14,7 +14,7 @@ if [ "$1" != "" ] && [ "${DP_AB:-0}" = "1" ]; then
   export DRAM_TUNING=1 DRAM_DIST_TRANSPORT=torch
   for spec in "1 f32" "2 bf16" "3 bf16"; do
     set -- $spec
-    python bench.py --config $1 --dtype $2 --force-dist --no-graph --steps 20 --warmup 5 --no-cpu-baseline --timeline off \
+    python bench.py --full --config $1 --dtype $2 --force-dist --no-graph --steps 20 --warmup 5 --no-cpu-baseline --timeline off \
         > $O/fd_torch_c$1_$2.json 2> $O/fd_torch_c$1_$2.err || echo "torch transport config $1 $2: rc=$?" >> $O/failures.txt
   done
 fi

@@ -14,11 +14,14 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bodyct-dram-emph-subtype_amd", "csrc")
 TABLE = "--table" in sys.argv
 files = [a for a in sys.argv[1:] if a != "--table"] or sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+# assembly goes to a directory of this run's own (a fixed name under /tmp belongs to whoever ran the tool first)
+TMP = tempfile.TemporaryDirectory(prefix="isa_waits_")
 
 
 def short_name(name):
@@ -29,7 +32,7 @@ def short_name(name):
 
 is_dma = lambda l: "global_load_lds" in l or ("buffer_load" in l and l.rstrip().endswith("lds"))   # noqa: E731
 for f in files:
-    out = f"/tmp/isa_{os.path.basename(f)}.s"
+    out = os.path.join(TMP.name, f"isa_{os.path.basename(f)}.s")
     r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
                         "-DDRAM_ABI_HASH=\"isa\"", "--offload-device-only", "-S", f, "-o", out], capture_output=True, text=True)
     if r.returncode:

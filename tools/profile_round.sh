@@ -14,23 +14,23 @@ O=$R/gpurun_out/prof
 mkdir -p $O
 cd $R
 if [ "$PHASE" = "all" ] || [ "$PHASE" = "bench" ]; then
-python bench.py --steps 20 --warmup 5 > $O/bench_config1.json.log 2>$O/bench_config1.err
-python bench.py --steps 5 --warmup 2 --no-cpu-baseline --detail $O/bench_config1_per_layer.txt > $O/bench_config1_detail.json.log 2>$O/bench_config1_detail.json.log.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_config1.json.log 2>$O/bench_config1.err
+python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --detail $O/bench_config1_per_layer.txt > $O/bench_config1_detail.json.log 2>$O/bench_config1_detail.json.log.err
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --timeline off --no-graph > $O/bench_config1_no_timeline.json.log 2>$O/bench_config1_no_timeline.json.log.err
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --timeline off --graph > $O/bench_config1_graph.json.log 2>$O/bench_config1_graph.json.log.err
-for c in 0 3 5; do python bench.py --config $c --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_config$c.json.log 2>$O/bench_config$c.json.log.err; done
+for c in 0 3 5; do python bench.py --full --config $c --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_config$c.json.log 2>$O/bench_config$c.json.log.err; done
 python bench.py --config 1 --graph --graph-streams 2 --steps 10 --warmup 3 --no-cpu-baseline --timeline off > $O/bench_config1_graph2.json.log 2>$O/bench_config1_graph2.json.log.err     # (default: one branch)
 python bench.py --config 3 --no-graph --steps 10 --warmup 3 --no-cpu-baseline --timeline off > $O/bench_config3_eager.json.log 2>$O/bench_config3_eager.json.log.err
 python bench.py --config 2 --no-graph --steps 10 --warmup 3 --no-cpu-baseline --timeline off > $O/bench_config2_eager.json.log 2>$O/bench_config2_eager.json.log.err
-python bench.py --config 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_config2.json.log 2>$O/bench_config2.json.log.err          # bf16, as specified
-python bench.py --config 2 --dtype f32 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_config2_f32.json.log 2>$O/bench_config2_f32.json.log.err
-python bench.py --config 3 --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_config3_bf16.json.log 2>$O/bench_config3_bf16.json.log.err
-python bench.py --config 4 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_config4.json.log 2>$O/bench_config4.json.log.err           # bf16 + recompute
+python bench.py --full --config 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_config2.json.log 2>$O/bench_config2.json.log.err          # bf16, as specified
+python bench.py --full --config 2 --dtype f32 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_config2_f32.json.log 2>$O/bench_config2_f32.json.log.err
+python bench.py --full --config 3 --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_config3_bf16.json.log 2>$O/bench_config3_bf16.json.log.err
+python bench.py --full --config 4 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_config4.json.log 2>$O/bench_config4.json.log.err           # bf16 + recompute
 # the data-parallel step at world size 1 with every collective in place (own RCCL communicators), next to the plain step
 # of the same process (plain_ms_per_step / exposed_collective_ms in each line)
 for spec in "1 f32" "2 bf16" "3 bf16"; do
   set -- $spec
-  python bench.py --config $1 --dtype $2 --force-dist --steps 20 --warmup 5 --no-cpu-baseline --timeline off > $O/bench_config$1_$2_forcedist.json.log 2>$O/bench_config$1_$2_forcedist.json.log.err
+  python bench.py --full --config $1 --dtype $2 --force-dist --steps 20 --warmup 5 --no-cpu-baseline --timeline off > $O/bench_config$1_$2_forcedist.json.log 2>$O/bench_config$1_$2_forcedist.json.log.err
 done
 fi
 if [ "$PHASE" = "bench" ]; then ls -la $O | head -60; exit 0; fi
