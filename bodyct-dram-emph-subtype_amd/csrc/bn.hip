@@ -301,8 +301,8 @@ __global__ void bn_apply_shortcut_a_kernel(const T* __restrict__ y, const float*
 // Column reductions over rows of an [rows][C] tensor.
 // MODE 0: partial[p][0][c] = sum a          (R = 1)
 // MODE 1: BN backward: g = dz*(z>0); partial[p][0][c] = sum g, partial[p][1][c] = sum g*xhat (R = 2)
-// U: rows per batch of loads (1: few registers, occupancy hides the latency -- the large tensors; 8: a grid of at most a
-// few workgroups per CU, where the rows in flight per thread are all the memory-level parallelism there is).
+// U: rows per batch of loads (8: a grid of at most a few workgroups per CU, where the rows in flight per thread are all
+// the memory-level parallelism there is; rows_per_block caps the grid at 1 024 row blocks, so U = 8 is the only form).
 template <int MODE, typename T, int U = 1>
 __global__ __launch_bounds__(256) void colreduce_kernel(const T* __restrict__ a, const T* __restrict__ zz,
                                                         const T* __restrict__ yy, const float* __restrict__ mean,
@@ -734,12 +734,9 @@ static int bn_bwd_reduce_impl(const T* dz, const T* z, const T* y, const float* 
   const int nparts = (int)((rows + rpb - 1) / rpb);
   DramProf prof(DRAM_FAM_BN, 3, 0.0, (double)sizeof(T) * (double)rows * C * (relu && z ? 3.0 : 2.0), (hipStream_t)stream);
   const int ychunks = ((C >> 2) + 255) / 256;        // 256-lane channel chunks (1 up to 1 024 channels)
-  if (nparts <= 1024)
-    hipLaunchKernelGGL((colreduce_kernel<1, T, 8>), dim3(nparts, ychunks), dim3(256), 0, (hipStream_t)stream, dz, z, y, mean,
-                       invstd, partial, (long)rows, C, rpb, relu, scale, shift);
-  else
-    hipLaunchKernelGGL((colreduce_kernel<1, T, 1>), dim3(nparts, ychunks), dim3(256), 0, (hipStream_t)stream, dz, z, y, mean,
-                       invstd, partial, (long)rows, C, rpb, relu, scale, shift);
+  // (rows_per_block keeps nparts <= 1 024 for every row count: one form, 8 rows per batch of loads)
+  hipLaunchKernelGGL((colreduce_kernel<1, T, 8>), dim3(nparts, ychunks), dim3(256), 0, (hipStream_t)stream, dz, z, y, mean,
+                     invstd, partial, (long)rows, C, rpb, relu, scale, shift);
   DRAM_LAUNCH_CHECK();
   return DRAM_OK;
 }
@@ -762,12 +759,8 @@ static int colsum_impl(const T* a, float* partial, long long rows, int C, dram_s
   const int nparts = (int)((rows + rpb - 1) / rpb);
   DramProf prof(DRAM_FAM_BN, 4, 0.0, (double)sizeof(T) * (double)rows * C, (hipStream_t)stream);
   const int ychunks = ((C >> 2) + 255) / 256;
-  if (nparts <= 1024)
-    hipLaunchKernelGGL((colreduce_kernel<0, T, 8>), dim3(nparts, ychunks), dim3(256), 0, (hipStream_t)stream, a,
-                       (const T*)nullptr, (const T*)nullptr, nullptr, nullptr, partial, (long)rows, C, rpb, 0);
-  else
-    hipLaunchKernelGGL((colreduce_kernel<0, T, 1>), dim3(nparts, ychunks), dim3(256), 0, (hipStream_t)stream, a,
-                       (const T*)nullptr, (const T*)nullptr, nullptr, nullptr, partial, (long)rows, C, rpb, 0);
+  hipLaunchKernelGGL((colreduce_kernel<0, T, 8>), dim3(nparts, ychunks), dim3(256), 0, (hipStream_t)stream, a,
+                     (const T*)nullptr, (const T*)nullptr, nullptr, nullptr, partial, (long)rows, C, rpb, 0);
   DRAM_LAUNCH_CHECK();
   return DRAM_OK;
 }
