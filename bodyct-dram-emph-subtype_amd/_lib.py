@@ -101,6 +101,8 @@ SIGNATURES = {
     "dram_stem_fwd": (I, [P, P, P, P, I, I, I, I, P]),
     "dram_stem_bwd_weight_workspace": (SZ, [I, I, I, I]),
     "dram_stem_bwd_weight": (I, [P, P, P, I, I, I, I, P, SZ, P]),
+    "dram_stem_bwd_data_workspace": (SZ, [I, I, I, I]),
+    "dram_stem_bwd_data": (I, [P, P, P, I, I, I, I, P, SZ, P]),
     "dram_reduce_partials_stages": (I, [I]),
     "dram_reduce_partials": (I, [P, P, P, I, I, I, D, I, P]),
     "dram_fold_partials_stages": (I, [I]),
@@ -112,6 +114,7 @@ SIGNATURES = {
     "dram_bn_bwd_reduce": (I, [P, P, P, P, P, P, P, P, LL, I, I, P]),
     "dram_bn_bwd_apply_nparts": (I, [LL, I]),
     "dram_bn_bwd_apply": (I, [P, P, P, P, P, P, P, P, P, D, P, P, P, LL, I, I, P]),
+    "dram_bn_bwd_apply_eval": (I, [P, P, P, P, P, P, P, LL, I, I, P]),
     "dram_colsum": (I, [P, P, LL, I, P]),
     "dram_maxpool_fwd": (I, [P, P, P, I, I, I, I, I, P]),
     "dram_maxpool_bwd": (I, [P, P, P, I, P, I, I, I, I, I, P]),
@@ -147,11 +150,13 @@ SIGNATURES = {
     "dram_conv3d_bwd_weight_bf16": (I, [P, P, P, DP, P, SZ, P]),
     "dram_stem_fwd_bf16": (I, [P, P, P, P, I, I, I, I, P]),
     "dram_stem_bwd_weight_bf16": (I, [P, P, P, I, I, I, I, P, SZ, P]),
+    "dram_stem_bwd_data_bf16": (I, [P, P, P, I, I, I, I, P, SZ, P]),
     "dram_stem_fwd_bf16mm": (I, [P, P, P, P, I, I, I, I, P]),
     "dram_stem_bwd_weight_bf16mm": (I, [P, P, P, I, I, I, I, P, SZ, P]),
     "dram_bn_apply_bf16": (I, [P, P, P, P, I, I, I, I, I, P, I, I, I, I, I, I, P]),
     "dram_bn_bwd_reduce_bf16": (I, [P, P, P, P, P, P, P, P, LL, I, I, P]),
     "dram_bn_bwd_apply_bf16": (I, [P, P, P, P, P, P, P, P, P, D, P, P, P, LL, I, I, P]),
+    "dram_bn_bwd_apply_eval_bf16": (I, [P, P, P, P, P, P, P, LL, I, I, P]),
     "dram_colsum_bf16": (I, [P, P, LL, I, P]),
     "dram_maxpool_fwd_bf16": (I, [P, P, P, I, I, I, I, I, P]),
     "dram_maxpool_bwd_bf16": (I, [P, P, P, I, P, I, I, I, I, I, P]),

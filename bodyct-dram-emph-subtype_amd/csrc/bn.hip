@@ -543,6 +543,69 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(const T* __restr
   }
 }
 
+// BatchNorm backward on the RUNNING statistics (eval mode): dy = scale * dz * mask -- no batch-mean terms, so no
+// dependence on a reduction.  The mask is read from z (y is then never touched) or re-derived from y with the forward's
+// fma.  Block b sweeps `per` consecutive quads (one-shot blocks: per = 4,096, grid = ceil(total4 / per); capped grid:
+// per = 256 and a grid-stride loop), four quads in flight per thread; with 256 % (C / 4) == 0 the thread's channel quad
+// is fixed and its column sums of dy (the bias gradient of a convolution in front) are folded per block in a fixed order.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_bwd_apply_eval_kernel(const T* __restrict__ dz, const T* __restrict__ z,
+                                                                const T* __restrict__ y, const float* __restrict__ scale,
+                                                                const float* __restrict__ shift, T* __restrict__ dy, int C,
+                                                                long total4, int relu, int per,
+                                                                float* __restrict__ colpart) {
+  const int Q = C >> 2;
+  float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long base = blockIdx.x * (long)per; base < total4; base += (long)gridDim.x * per) {
+    for (int j0 = 0; j0 < per; j0 += 1024) {
+      float4 g[4], m[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long i = base + j0 + 256 * u + threadIdx.x;
+        if (j0 + 256 * u < per && i < total4) {
+          g[u] = ld4<T>(dz, 4 * i);
+          if (relu) m[u] = z ? ld4<T>(z, 4 * i) : ld4<T>(y, 4 * i);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long i = base + j0 + 256 * u + threadIdx.x;
+        if (j0 + 256 * u < per && i < total4) {
+          const int c = 4 * (int)(i % Q);
+          const float4 sc = *reinterpret_cast<const float4*>(scale + c);
+          float4 gg = g[u];
+          if (relu) {
+            float4 zv = m[u];
+            if (!z) {
+              const float4 sh = *reinterpret_cast<const float4*>(shift + c);
+              zv = make_float4(__builtin_fmaf(zv.x, sc.x, sh.x), __builtin_fmaf(zv.y, sc.y, sh.y),
+                               __builtin_fmaf(zv.z, sc.z, sh.z), __builtin_fmaf(zv.w, sc.w, sh.w));
+            }
+            gg.x = zv.x > 0.f ? gg.x : 0.f; gg.y = zv.y > 0.f ? gg.y : 0.f;
+            gg.z = zv.z > 0.f ? gg.z : 0.f; gg.w = zv.w > 0.f ? gg.w : 0.f;
+          }
+          const float4 o = make_float4(sc.x * gg.x, sc.y * gg.y, sc.z * gg.z, sc.w * gg.w);
+          st4<T>(dy, 4 * i, o);
+          cs.x += o.x; cs.y += o.y; cs.z += o.z; cs.w += o.w;
+        }
+      }
+    }
+  }
+  if (colpart) {
+    __shared__ float4 sm[256];
+    sm[threadIdx.x] = cs;
+    __syncthreads();
+    if ((int)threadIdx.x < Q) {
+      float4 t = sm[threadIdx.x];
+      for (int k = threadIdx.x + Q; k < 256; k += Q) {
+        const float4 u = sm[k];
+        t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
+      }
+      *reinterpret_cast<float4*>(colpart + (long)blockIdx.x * C + 4 * threadIdx.x) = t;
+    }
+  }
+}
+
 __global__ void add_kernel(const float4* __restrict__ a, const float4* __restrict__ b, float4* __restrict__ o,
                            long n4, const float* __restrict__ as, const float* __restrict__ bs,
                            float* __restrict__ os, long n) {
@@ -824,6 +887,34 @@ extern "C" int dram_bn_bwd_apply_bf16(const void* dz, const void* z, const void*
                                       float* colsum_partial, long long rows, int C, int relu, dram_stream_t stream) {
   return bn_bwd_apply_impl<bf16_t>((const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, mean, invstd, gamma, scale,
                                    shift, sums, count, count_dev, (bf16_t*)dy, colsum_partial, rows, C, relu, stream);
+}
+
+template <typename T>
+static int bn_bwd_apply_eval_impl(const T* dz, const T* z, const T* y, const float* scale, const float* shift, T* dy,
+                                  float* colsum_partial, long long rows, int C, int relu, dram_stream_t stream) {
+  if (!dz || !scale || !dy || rows < 1 || C < 4 || (C & 3)) return DRAM_ERR_BAD_ARG;
+  if (relu && !z && !(y && shift)) return DRAM_ERR_BAD_ARG;
+  if (colsum_partial && dram_bn_bwd_apply_nparts(rows, C) < 1) return DRAM_ERR_UNSUPPORTED;
+  const long total4 = (long)rows * (C >> 2);
+  DramProf prof(DRAM_FAM_BN, 11, 0.0, 4.0 * sizeof(T) * (double)total4 * (relu ? 3.0 : 2.0), (hipStream_t)stream);
+  // (the grid is what dram_bn_bwd_apply_nparts reports: one partial row per block)
+  const int per = ew_shape() == 0 ? 256 : 4096;
+  const int grid = ew_shape() == 0 ? ew_grid(total4) : ew_blocks(total4, 4096, 0);
+  hipLaunchKernelGGL((bn_bwd_apply_eval_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dz, z, y, scale, shift,
+                     dy, C, total4, relu, per, colsum_partial);
+  DRAM_LAUNCH_CHECK();
+  return DRAM_OK;
+}
+extern "C" int dram_bn_bwd_apply_eval(const float* dz, const float* z, const float* y, const float* scale,
+                                      const float* shift, float* dy, float* colsum_partial, long long rows, int C,
+                                      int relu, dram_stream_t stream) {
+  return bn_bwd_apply_eval_impl<float>(dz, z, y, scale, shift, dy, colsum_partial, rows, C, relu, stream);
+}
+extern "C" int dram_bn_bwd_apply_eval_bf16(const void* dz, const void* z, const void* y, const float* scale,
+                                           const float* shift, void* dy, float* colsum_partial, long long rows, int C,
+                                           int relu, dram_stream_t stream) {
+  return bn_bwd_apply_eval_impl<bf16_t>((const bf16_t*)dz, (const bf16_t*)z, (const bf16_t*)y, scale, shift, (bf16_t*)dy,
+                                        colsum_partial, rows, C, relu, stream);
 }
 
 extern "C" int dram_add(const float* a, const float* b, float* out, long long n, dram_stream_t stream) {

@@ -1,6 +1,7 @@
 // stem.hip -- Conv3d(1, 64, k=7, s=2, p=3, bias=False): forward and weight gradient.
 // Replaces nn.Conv3d at reference med3d.py:196-202 / :296-302 (fwd :272 / :371) and its
-// autograd weight gradient.  (No data gradient: the network input needs none.)
+// autograd weight gradient.  (The data gradient -- the gradient of the input volume, for attribution -- is
+// stem_dgrad.hip; a training step never launches it.)
 //
 // C_in = 1, so there is no channel row to gather: the im2col operand is read straight
 // out of an LDS-resident input patch.  Forward: workgroup = 4x8x8 output voxels x 64

@@ -39,8 +39,13 @@ class _State:
     """Per-call state: parameter/buffer dicts, flags, saved contexts, gradient sink."""
 
     def __init__(self, P: Dict[str, Tensor], training: bool, need_grad: bool, dist=None, recompute: bool = False,
-                 storage=torch.float32):
+                 storage=torch.float32, need_x: bool = False, need_param: Optional[bool] = None):
         self.P = P
+        # what backward has to produce: the gradient of the input volume (stem data gradient), and / or parameter
+        # gradients.  Neither asked for explicitly = the training step (parameters only).
+        self.need_x = bool(need_x) and need_grad
+        self.need_param = need_grad and (True if need_param is None else bool(need_param))
+        self.eval_ss: Dict[str, tuple] = {}   # eval mode with gradients: BatchNorm prefix -> (scale, shift) of the forward
         self.storage = storage        # storage type of the activations: float32, or bfloat16 (`--precision bf16`)
         self.training = training
         self.need_grad = need_grad
@@ -100,6 +105,8 @@ class Engine:
             mean, invstd, scale, shift = ops.bn_finalize(None, 1.0, P[bnp + ".weight"], P[bnp + ".bias"],
                                                          P[bnp + ".running_mean"], P[bnp + ".running_var"],
                                                          BN_MOMENTUM, BN_EPS, False)
+            if st.need_grad:
+                st.eval_ss[bnp] = (scale, shift)
         if not apply:
             z = None
         elif pool:
@@ -109,7 +116,32 @@ class Engine:
         # without a residual the backward pass re-derives the ReLU mask from y (scale, shift) instead of reading z
         return z, mean, invstd, (count, count_dev), (None if residual is not None else (scale, shift))
 
+    def _bn_bwd_eval(self, st: _State, c: dict, dz: Tensor) -> Tensor:
+        """BatchNorm on its running statistics: dy = scale * dz * mask -- one pass, no batch-mean terms, no SyncBN
+        exchange.  The parameter gradients (and the bias gradient of a convolution in front) only where a parameter
+        wants one: dgamma = sum g * xhat, dbeta = sum g with xhat from the running statistics."""
+        bnp = c["bn"]
+        scale, shift = st.eval_ss[bnp]
+        zmask = c["z"] if c.get("ss") is None else None
+        if st.dist is not None:
+            self._flush_wgrad(st)
+        if st.need_param:
+            part = ops.bn_bwd_reduce(dz, zmask, c["y"], c["mean"], c["invstd"], True, scale, shift)
+            _, sf = ops.reduce_partials(part, want_f32=True)
+            st.grads[bnp + ".weight"] = sf[1]
+            st.grads[bnp + ".bias"] = sf[0]
+        y = c["y"] if zmask is None else None
+        if c.get("b") and st.need_param:
+            dy, colpart = ops.bn_bwd_apply_eval(dz, zmask, y, scale, shift, True, want_colsum=True)
+            if colpart is None:
+                colpart = ops.colsum(dy)
+            st.grads[c["b"]] = ops.reduce_partials(colpart)[0].float()
+            return dy
+        return ops.bn_bwd_apply_eval(dz, zmask, y, scale, shift, True)
+
     def _bn_bwd(self, st: _State, c: dict, dz: Tensor) -> Tensor:
+        if not st.training:
+            return self._bn_bwd_eval(st, c, dz)
         bnp = c["bn"]
         zmask, (sc, sh) = (c["z"], (None, None)) if c.get("ss") is None else (None, c["ss"])
         part = c.pop("part", None)      # taken by the data gradient that produced dz (_conv_bn_bwd, nxt), or a pass here
@@ -179,10 +211,10 @@ class Engine:
             wf, wb = ops.packed_forward_weight(w, g, st.storage), None
         if split is not None:
             y, sp, v = ops.conv3d_fwd_cat(split[0], split[1], wf, st.P[bname] if bname else None, g, st.training,
-                                          st.need_grad and not st.recompute)
+                                          st.need_param and not st.recompute)
         else:
             y, sp, v = ops.conv3d_fwd_keep(x, wf, st.P[bname] if bname else None, g, st.training,
-                                           st.need_grad and not st.recompute, prologue=pro)
+                                           st.need_param and not st.recompute, prologue=pro)
         defer_z = defer_z and residual is None
         z, mean, invstd, count, ss = self._bn_fwd(st, y, sp, bnp, residual, rs, apply=not defer_z)
         c = None
@@ -201,7 +233,9 @@ class Engine:
         gradient is that unit's dz.  Where the data gradient can take that unit's backward statistics on its way out
         (ops.conv_bwd_bnstats_ok) they are left in nxt['part'] and its _bn_bwd skips the pass over dz and y."""
         dy = self._bn_bwd(st, c, dz)
-        if st.side is not None:
+        if not st.need_param:
+            pass                                        # attribution only: the data-gradient chain alone
+        elif st.side is not None:
             # second stream: concurrent with the data-gradient chain (and, data parallel, with the host-visible
             # wait for the next unit's statistic all-reduce: the GPU keeps executing this kernel meanwhile)
             self._wgrad_side(st, c, dy)
@@ -213,7 +247,7 @@ class Engine:
             self._wgrad(st, c, dy)
         if not need_dx:
             return None
-        if (nxt is not None and add is None and gate is None and nxt.get("ss") is not None
+        if (st.training and nxt is not None and add is None and gate is None and nxt.get("ss") is not None
                 and ops.conv_bwd_bnstats_ok(c["g"], dy.dtype)):
             dx, nxt["part"] = ops.conv3d_bwd_data_bnstats(dy, c["wb"], c["g"], nxt["y"], nxt["mean"], nxt["invstd"],
                                                           *nxt["ss"], overlapped=st.side is not None)
@@ -365,7 +399,9 @@ class Engine:
         dy = self._bn_bwd(st, c, dz)
         c["h"] = ops.upmix_gather_bwd(dy)               # read by the weight gradient (side stream) and the data gradient
         h = c["h"]
-        if st.side is not None:
+        if not st.need_param:
+            c["h"] = None
+        elif st.side is not None:
             self._wgrad_side(st, c, dy)
         elif st.dist is not None:
             st.deferred = (c, dy)
@@ -419,19 +455,26 @@ class Engine:
 
     # ------------------------------------------------------------------ whole network
     def forward(self, P: Dict[str, Tensor], x: Tensor, lungs: Optional[Tensor], training: bool, need_grad: bool,
-                dist=None, recompute: bool = False, storage=torch.float32):
+                dist=None, recompute: bool = False, storage=torch.float32, need_x: bool = False,
+                need_param: Optional[bool] = None):
         """x [B,1,D,H,W] (NCDHW == NDHW for C=1), lungs None or [B,1,D,H,W] float.
         Returns (dense_list, outs_list, saved-or-None).  Every kernel is launched on x's device (its
         current stream); operands on any other device are rejected before launch.
         storage: float32 (the reference's default arithmetic) or bfloat16 -- activations and saved tensors in bf16,
         products of bf16 operands accumulated in fp32, statistics / parameters / weight gradients / dense head
-        outputs in fp32 (the reference under `--precision bf16`, train.py:46)."""
+        outputs in fp32 (the reference under `--precision bf16`, train.py:46).
+        need_grad: keep what backward needs.  need_x: backward also returns the gradient of x (saved['dx'], the stem data
+        gradient -- launched only then).  need_param (default: need_grad): parameter gradients are wanted; False =
+        attribution only: backward runs the data-gradient chain alone -- no weight-gradient kernel, no BatchNorm
+        parameter reduction in eval mode, no second stream.  It is all or nothing: a partially frozen parameter set
+        computes every parameter gradient, as before, and the caller drops what it does not want.
+        training=False with need_grad: BatchNorm on its running statistics in both directions, no buffer is touched."""
         if storage not in (torch.float32, torch.bfloat16):
             raise NotImplementedError(f"activation storage type {storage}")
         with ops.launch_scope(x.device):
             if need_grad:
                 self._throttle()
-            return self._forward(P, x, lungs, training, need_grad, dist, recompute, storage)
+            return self._forward(P, x, lungs, training, need_grad, dist, recompute, storage, need_x, need_param)
 
     def backward(self, saved: dict, g_dense: List[Optional[Tensor]], g_outs: List[Optional[Tensor]]):
         with ops.launch_scope(saved["dense"].device):
@@ -514,13 +557,12 @@ class Engine:
             st.packed_ready = torch.cuda.Event()
             st.packed_ready.record(side)
 
-    def _forward(self, P, x, lungs, training, need_grad, dist, recompute=False, storage=torch.float32):
-        if need_grad and not training:
-            raise NotImplementedError("gradients through eval-mode BatchNorm are not part of the hot path")
-        st = _State(P, training, need_grad, dist, recompute, storage)
+    def _forward(self, P, x, lungs, training, need_grad, dist, recompute=False, storage=torch.float32, need_x=False,
+                 need_param=None):
+        st = _State(P, training, need_grad, dist, recompute, storage, need_x, need_param)
         B, _, D, H, W = x.shape
         shape_key = (tuple(x.shape), storage, x.device.index)
-        if need_grad:
+        if st.need_param:                               # (attribution only: no second stream, weights packed in place)
             self._prepack(st, shape_key)
         x4 = x.reshape(B, D, H, W)
         lungs4 = None if lungs is None else lungs.reshape(B, *lungs.shape[-3:]).contiguous()
@@ -574,9 +616,10 @@ class Engine:
 
     def _backward(self, saved, g_dense, g_outs):
         st: _State = saved["st"]
-        if st.dist is not None:
-            st.dist.begin_backward(saved["dense"].device)
-        if self._two_streams():
+        dist = st.dist if st.need_param else None       # (no parameter gradient: nothing to reduce)
+        if dist is not None:
+            dist.begin_backward(saved["dense"].device)
+        if st.need_param and self._two_streams():
             st.side = ops.side_stream(saved["dense"].device.index)
 
         n0, n1 = saved["n0"], saved["n1"]
@@ -607,13 +650,14 @@ class Engine:
                 gd[:, n0:] = g_dense[1]
         dxup3, wpart = ops.head_bwd(saved["xup3"], saved["hw"], dense if sig else None, gd, gpool,
                                     saved["lungs4"] if sig else None, sig)
-        wg = ops.reduce_partials(wpart.reshape(wpart.shape[0], 1, NO * 33)).reshape(NO, 33).float()
-        st.grads["fcs.0.weight"] = wg[:n0, :32].reshape(n0, 32, 1, 1, 1).contiguous()
-        st.grads["fcs.0.bias"] = wg[:n0, 32].contiguous()
-        st.grads["fcs.1.weight"] = wg[n0:, :32].reshape(n1, 32, 1, 1, 1).contiguous()
-        st.grads["fcs.1.bias"] = wg[n0:, 32].contiguous()
-        if st.dist is not None:
-            st.dist.grads_ready(st.grads, ["fcs.0.weight", "fcs.0.bias", "fcs.1.weight", "fcs.1.bias"])
+        if st.need_param:
+            wg = ops.reduce_partials(wpart.reshape(wpart.shape[0], 1, NO * 33)).reshape(NO, 33).float()
+            st.grads["fcs.0.weight"] = wg[:n0, :32].reshape(n0, 32, 1, 1, 1).contiguous()
+            st.grads["fcs.0.bias"] = wg[:n0, 32].contiguous()
+            st.grads["fcs.1.weight"] = wg[n0:, :32].reshape(n1, 32, 1, 1, 1).contiguous()
+            st.grads["fcs.1.bias"] = wg[n0:, 32].contiguous()
+        if dist is not None:
+            dist.grads_ready(st.grads, ["fcs.0.weight", "fcs.0.bias", "fcs.1.weight", "fcs.1.bias"])
 
         dxup2 = self._conv_bn_bwd(st, saved["cu3"], dxup3, nxt=saved["cu2"][1])
         dxup1, dskip_stem = self._up_bwd(st, saved["cu2"], dxup2, skip_view=True)   # consumed by maxpool_bwd
@@ -634,13 +678,18 @@ class Engine:
         c0 = dict(z=saved["xs"], y=saved["y0"], mean=saved["mean0"], invstd=saved["invstd0"], count=saved["count0"],
                   bn="bn1", ss=saved["ss0"])
         dy0 = self._bn_bwd(st, c0, dxs)
-        st.grads["conv1.weight"] = ops.stem_bwd_weight(saved["x4"], dy0,
-                                                       out=st.dist.grad_out("conv1.weight") if st.dist else None)
+        if st.need_param:
+            st.grads["conv1.weight"] = ops.stem_bwd_weight(saved["x4"], dy0,
+                                                           out=dist.grad_out("conv1.weight") if dist else None)
+        if st.need_x:
+            # the gradient of the volume itself (local under data parallelism: the input is this rank's)
+            x4 = saved["x4"]
+            saved["dx"] = ops.stem_bwd_data(dy0, st.P["conv1.weight"], x4.shape).reshape(x4.shape[0], 1, *x4.shape[1:])
         if st.side is not None:
             torch.cuda.current_stream().wait_stream(st.side)      # every weight gradient is final from here on
-        if st.dist is not None:
-            st.dist.grads_ready(st.grads, ["conv1.weight", "bn1.weight", "bn1.bias"])
-            st.dist.finish(st.grads)
+        if dist is not None:
+            dist.grads_ready(st.grads, ["conv1.weight", "bn1.weight", "bn1.bias"])
+            dist.finish(st.grads)
         return st.grads
 
 

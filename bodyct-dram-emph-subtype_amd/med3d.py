@@ -89,8 +89,11 @@ class _Med3DFunction(torch.autograd.Function):
     def forward(ctx, module, x, lungs, *params):
         ctx.set_materialize_grads(False)
         P = module._tensor_dict()
+        # (x, then the parameters; a partially frozen parameter set computes every parameter gradient, as before)
+        need_x, need_param = ctx.needs_input_grad[1], any(ctx.needs_input_grad[3:])
         dense, outs, saved = module._engine.forward(P, x, lungs, module.training, True, module._dist,
-                                                    module.activation_recompute, module._storage_now())
+                                                    module.activation_recompute, module._storage_now(),
+                                                    need_x=need_x, need_param=need_param)
         ctx.saved_state = saved
         ctx.module = module
         return dense[0], dense[1], outs[0], outs[1]
@@ -106,7 +109,7 @@ class _Med3DFunction(torch.autograd.Function):
             return None if t is None else t.contiguous()
 
         grads = module._engine.backward(saved, [c(gd0), c(gd1)], [c(go0), c(go1)])
-        out = [None, None, None]
+        out = [None, saved.get("dx") if ctx.needs_input_grad[1] else None, None]     # (no gradient for lungs)
         for name, p in module._named_tensors()[0]:
             out.append(grads.get(name) if p.requires_grad else None)
         return tuple(out)
@@ -200,7 +203,7 @@ class _ResNetSeg(nn.Module):
         d.update(bufs)
         return d
 
-    def forward(self, x: torch.Tensor, lungs: Optional[torch.Tensor] = None):
+    def _check_input(self, x):
         if not x.is_cuda:
             raise RuntimeError("bodyct-dram-emph-subtype_amd runs on MI355X only: input is on "
                                f"{x.device}; there is no CPU fallback (the CPU oracle lives in oracle/ for tests)")
@@ -209,11 +212,17 @@ class _ResNetSeg(nn.Module):
         if any(int(s) % 8 for s in x.shape[-3:]):
             # crop_concat_5d (med3d.py:39-48) mis-crops otherwise; the reference only asserts on W
             raise ValueError("input D,H,W must be multiples of 8")
+
+    def forward(self, x: torch.Tensor, lungs: Optional[torch.Tensor] = None):
+        """-> (dense_outs, outs).  Differentiable with respect to the parameters and to x (`x.requires_grad_()`; not to
+        lungs), in train() and in eval() mode -- eval: BatchNorm on its running statistics in both directions, no
+        buffer touched.  When no parameter requires a gradient, backward runs the data-gradient chain only."""
+        self._check_input(x)
         x = x.contiguous().float()
         if lungs is not None:
             lungs = lungs.contiguous().float()
         params = [p for _, p in self._named_tensors()[0]]
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         if need_grad:
             d0, d1, o0, o1 = _Med3DFunction.apply(self, x, lungs, *params)
             return [d0, d1], [o0, o1]
@@ -221,6 +230,46 @@ class _ResNetSeg(nn.Module):
             dense, outs, _ = self._engine.forward(self._tensor_dict(), x, lungs, self.training, False, self._dist,
                                                   storage=self._storage_now())
         return dense, outs
+
+    def input_gradient(self, x: torch.Tensor, lungs: Optional[torch.Tensor] = None, *, out_grads,
+                       dense_grads=None) -> torch.Tensor:
+        """Gradient of a score with respect to the volume: runs forward(x, lungs) in the module's current mode
+        (eval(): running statistics, nothing updated; train(): a training forward, running statistics included) and
+        backward from the given cotangents -- out_grads = (g0, g1) for `outs`, dense_grads = (g0, g1) for `dense_outs`,
+        each a tensor shaped like its output or None -- along the data-gradient chain only: no weight-gradient kernel
+        runs and no parameter's .grad is touched.  Returns [B,1,D,H,W] float32, bit-identical to x.grad of the
+        `x.requires_grad_()` + backward() route.  Under distributed.attach the result is local to the rank."""
+        self._check_input(x)
+        x = x.detach().contiguous().float()
+        if lungs is not None:
+            lungs = lungs.detach().contiguous().float()
+
+        def pair(gs, name):
+            gs = [None, None] if gs is None else list(gs)
+            if len(gs) != 2:
+                raise ValueError(f"{name}: expected two cotangents (or None), got {len(gs)}")
+            return gs
+
+        og, dg = pair(out_grads, "out_grads"), pair(dense_grads, "dense_grads")
+        if all(g is None for g in og + dg):
+            raise ValueError("input_gradient: every cotangent is None")
+        for gs, name in ((og, "out_grads"), (dg, "dense_grads")):      # before anything is launched (or updated)
+            for i, g in enumerate(gs):
+                if g is not None and (not isinstance(g, torch.Tensor) or g.device != x.device):
+                    raise ValueError(f"{name}[{i}]: expected a tensor on {x.device} (or None)")
+        with torch.no_grad():
+            dense, outs, saved = self._engine.forward(self._tensor_dict(), x, lungs, self.training, True, self._dist,
+                                                      self.activation_recompute, self._storage_now(),
+                                                      need_x=True, need_param=False)
+            for gs, ys, name in ((og, outs, "out_grads"), (dg, dense, "dense_grads")):
+                for i, (g, y) in enumerate(zip(gs, ys)):
+                    if g is None:
+                        continue
+                    if not isinstance(g, torch.Tensor) or g.device != y.device or tuple(g.shape) != tuple(y.shape):
+                        raise ValueError(f"{name}[{i}]: expected a tensor of shape {tuple(y.shape)} on {y.device}")
+                    gs[i] = g.detach().float().contiguous()
+            self._engine.backward(saved, dg, og)
+        return saved["dx"]
 
 
 class ResNetSegCls(_ResNetSeg):

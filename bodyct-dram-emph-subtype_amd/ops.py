@@ -874,6 +874,23 @@ def stem_bwd_weight(x: Tensor, dy: Tensor, out: Optional[Tensor] = None) -> Tens
     return dw
 
 
+def stem_bwd_data(dy: Tensor, w: Tensor, in_shape) -> Tensor:
+    """Data gradient of the stem convolution: dy [B,Do,Ho,Wo,64] (float32 or bfloat16), w [64,1,7,7,7] -> dx [B,D,H,W]
+    float32 for in_shape = (B, D, H, W).  fp32 arithmetic, deterministic (two launches: scatter GEMM + ordered fold)."""
+    B, D, H, W = (int(v) for v in in_shape)
+    if min(B, D, H, W) < 1:
+        raise ValueError(f"stem_bwd_data: bad input shape {tuple(in_shape)}")
+    sfx = _act(dy, "dy", (B, stem_out(D), stem_out(H), stem_out(W), 64))
+    _req(w, "w", shape=(64, 1, 7, 7, 7))
+    nbytes = _L().dram_stem_bwd_data_workspace(B, D, H, W)
+    ws = torch.empty(((nbytes + 3) // 4,), device=dy.device, dtype=torch.float32)
+    dx = torch.empty((B, D, H, W), device=dy.device, dtype=torch.float32)
+    with _span("stem_dgrad_kernel+fold", 2.0 * dy.numel() * 343):
+        _chk(_fn("dram_stem_bwd_data", sfx)(_p(dy), _p(w), _p(dx), B, D, H, W, _p(ws), nbytes, _stream()),
+             "dram_stem_bwd_data" + sfx)
+    return dx
+
+
 # --------------------------------------------------------------------------- batch norm
 FOLD_TICKET_DOUBLES = 256       # include/dram_hip.h DRAM_FOLD_TICKET_DOUBLES: per-call ticket words behind the stage rows
 
@@ -1023,6 +1040,34 @@ def bn_bwd_apply(dz: Tensor, z: Optional[Tensor], y: Tensor, mean: Tensor, invst
     _chk(_fn("dram_bn_bwd_apply", sfx)(_p(dz), _p(z), _p(y), _p(mean), _p(invstd), _p(gamma), _p(scale), _p(shift), _p(sums),
                                        float(count), _p(count_dev), _p(dy), _p(colpart), _rows(y), C, int(relu), _stream()),
          "dram_bn_bwd_apply")
+    return (dy, colpart) if want_colsum else dy
+
+
+def bn_bwd_apply_eval(dz: Tensor, z: Optional[Tensor], y: Optional[Tensor], scale: Tensor, shift: Optional[Tensor],
+                      relu: bool, want_colsum: bool = False):
+    """Backward of a BatchNorm that ran on its running statistics: dy = scale * dz * mask, the mask from z (y is not
+    read and may be None) or, z None, re-derived from y with the forward's scale / shift.
+    -> dy, or (dy, partial [P,1,C] column sums of dy) with want_colsum (None when C is unsupported there)."""
+    sfx = _act(dz, "dz")
+    C = dz.shape[-1]
+    _req(scale, "scale", shape=(C,))
+    if relu and z is not None:
+        _act(z, "z", dz.shape, like=dz)
+        y = None
+    elif relu:
+        if y is None or shift is None:
+            raise ValueError("BN backward with ReLU needs z, or y with scale and shift")
+        _act(y, "y", dz.shape, like=dz)
+        _req(shift, "shift", shape=(C,))
+    colpart = None
+    if want_colsum:
+        npart = _L().dram_bn_bwd_apply_nparts(_rows(dz), C)
+        if npart >= 1:
+            colpart = torch.empty((npart, 1, C), device=dz.device, dtype=torch.float32)
+    dy = torch.empty_like(dz)
+    _chk(_fn("dram_bn_bwd_apply_eval", sfx)(_p(dz), _p(z) if relu else None, _p(y) if relu else None, _p(scale),
+                                            _p(shift) if relu else None, _p(dy), _p(colpart), _rows(dz), C, int(relu),
+                                            _stream()), "dram_bn_bwd_apply_eval")
     return (dy, colpart) if want_colsum else dy
 
 

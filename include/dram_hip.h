@@ -72,7 +72,7 @@ enum {
   DRAM_FAM_WGRAD_W2D,       /* in-plane Winograd weight gradient (+ reduce)       (mfma) */
   DRAM_FAM_CONV_IGEMM,      /* direct implicit-GEMM conv, fwd + dgrad             (mfma) */
   DRAM_FAM_CONV_WGRAD,      /* direct weight gradient (+ reduce)                  (mfma) */
-  DRAM_FAM_STEM,            /* 7x7x7 stem conv fwd + wgrad                        (mfma) */
+  DRAM_FAM_STEM,            /* 7x7x7 stem conv fwd + wgrad + dgrad (variants 4, 5) (mfma) */
   DRAM_FAM_BN,              /* BN apply / backward / statistics folds / add       (hbm)  */
   DRAM_FAM_POOL_UP,         /* max-pool, upsample+concat, up-projection           (hbm)  */
   DRAM_FAM_HEAD_LOSS,       /* heads, dRAM losses                                 (hbm)  */
@@ -291,6 +291,13 @@ int dram_stem_fwd(const float* x, const float* w, float* y, float* stats_partial
 size_t dram_stem_bwd_weight_workspace(int B, int D, int H, int W);
 int dram_stem_bwd_weight(const float* x, const float* dy, float* dw, int B, int D, int H, int W,
                          void* workspace, size_t workspace_bytes, dram_stream_t stream);
+/* Data gradient (the transposed convolution): dx[b,d,h,w] = sum_c sum_k dy[b,od,oh,ow,c] * w[c,0,kd,kh,kw] over
+ * 2*od + kd - 3 == d (h, w likewise), dx [B,D,H,W] fp32.  Two launches: the scatter GEMM taps x voxels (K = 64) of
+ * every 4x8x8 block of dy voxels, overlap-added into that block's 13x21x21 input patch (workspace), and a fold of
+ * the overlapping patches in a fixed order -- deterministic, no atomics.  Any D, H, W >= 1. */
+size_t dram_stem_bwd_data_workspace(int B, int D, int H, int W);
+int dram_stem_bwd_data(const float* dy, const float* w, float* dx, int B, int D, int H, int W, void* workspace,
+                       size_t workspace_bytes, dram_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
 /* BatchNorm3d (+ReLU, + residual) -- med3d.py:121-124,133-142,153-182,203-204,227-228.
@@ -359,6 +366,12 @@ int dram_bn_bwd_apply(const float* dz, const float* z, const float* y, const flo
                       const float* invstd, const float* gamma, const float* scale, const float* shift,
                       const double* sums, double count, const double* count_dev, float* dy,
                       float* colsum_partial, long long rows, int C, int relu, dram_stream_t stream);
+/* phase 2 of a BatchNorm that ran on its RUNNING statistics (eval mode): dy = scale * g, scale = gamma *
+ * invstd_running as dram_bn_finalize(sums == NULL) returns it; no batch-mean terms, so it needs no phase 1 (that one,
+ * with the running mean / invstd, gives the parameter gradients where they are wanted).  The ReLU mask comes from z,
+ * and then y is not read and may be NULL, or (z == NULL) from fma(y, scale, shift) > 0.  colsum_partial as above. */
+int dram_bn_bwd_apply_eval(const float* dz, const float* z, const float* y, const float* scale, const float* shift,
+                           float* dy, float* colsum_partial, long long rows, int C, int relu, dram_stream_t stream);
 /* partial[p][0][c] = sum_rows a[row][c]  (conv-bias gradient) */
 int dram_colsum(const float* a, float* partial, long long rows, int C, dram_stream_t stream);
 
@@ -605,6 +618,9 @@ int dram_stem_fwd_bf16(const float* x, const float* w, void* y, float* stats_par
                        dram_stream_t stream);
 int dram_stem_bwd_weight_bf16(const float* x, const void* dy, float* dw, int B, int D, int H, int W, void* workspace,
                               size_t workspace_bytes, dram_stream_t stream);
+/* dy in bf16, widened on load; fp32 MFMA arithmetic, dx fp32 (same workspace) */
+int dram_stem_bwd_data_bf16(const void* dy, const float* w, float* dx, int B, int D, int H, int W, void* workspace,
+                            size_t workspace_bytes, dram_stream_t stream);
 /* the same two on the bf16 matrix cores (input rounded to bf16 on its way into LDS, weights rounded per launch;
  * same tile geometry, statistic rows and workspace as the fp32-MFMA forms above) */
 int dram_stem_fwd_bf16mm(const float* x, const float* w, void* y, float* stats_partial, int B, int D, int H, int W,
@@ -621,6 +637,8 @@ int dram_bn_bwd_apply_bf16(const void* dz, const void* z, const void* y, const f
                            const float* gamma, const float* scale, const float* shift, const double* sums, double count,
                            const double* count_dev, void* dy, float* colsum_partial, long long rows, int C, int relu,
                            dram_stream_t stream);
+int dram_bn_bwd_apply_eval_bf16(const void* dz, const void* z, const void* y, const float* scale, const float* shift,
+                                void* dy, float* colsum_partial, long long rows, int C, int relu, dram_stream_t stream);
 int dram_colsum_bf16(const void* a, float* partial, long long rows, int C, dram_stream_t stream);
 int dram_maxpool_fwd_bf16(const void* x, void* y, uint8_t* argmax, int B, int D, int H, int W, int C,
                           dram_stream_t stream);
