@@ -40,9 +40,9 @@ def _read(path: str) -> bytes:
 
 
 def abi_hash() -> str:
-    """Fingerprint of the C ABI = sha1 of include/dram_hip.h.  Compiled into the library
-    (dram_abi_hash()) and compared by _lib.load(): a library built from another header is
-    refused instead of being called with shifted arguments."""
+    """Fingerprint of the C ABI = sha1 of include/dram_hip.h, the file _lib parses its prototypes, structs and
+    constants from.  Compiled into the library (dram_abi_hash()) and compared by _lib.load(): a library built from
+    another header than the one the binding was read from is refused instead of being called with shifted arguments."""
     return hashlib.sha1(_read(os.path.join(INCLUDE, "dram_hip.h"))).hexdigest()[:16]
 
 

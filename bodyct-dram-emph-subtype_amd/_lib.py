@@ -1,4 +1,8 @@
-"""ctypes binding of libdram_hip.so (the C ABI declared in include/dram_hip.h).
+"""ctypes binding of libdram_hip.so, read from include/dram_hip.h.
+
+The header is the only description of the C ABI on the host side: at import it is parsed into ``SIGNATURES``
+(name -> (restype, argtypes)), the ``ctypes.Structure`` classes of its structs and its integer ``#define`` constants.
+``load()`` sets these prototypes on a library that carries the fingerprint of the same header file.
 
 The product path has NO fallback: if the library is missing or fails to load,
 ``load()`` raises.  ``import torch`` happens first on purpose -- libdram_hip.so needs
@@ -9,184 +13,103 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
+import re
+from ctypes import c_void_p
 
 import torch  # noqa: F401  (must precede CDLL: loads the HIP runtime we bind to)
 
 from . import _build
 
-P, I, LL, F, D, SZ = c_void_p, c_int, c_longlong, c_float, c_double, c_size_t
+# C type -> ctypes type, for parameters, return values and struct fields; `typedef void* NAME;` adds NAME (dram_stream_t)
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong,
+            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+            "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
+_POINTEES = set(_SCALARS) | {"void", "char", "uint8_t"}      # ... and the header's structs; any pointer is a c_void_p
+_ID = r"[A-Za-z_]\w*"
+_DECLARATOR = re.compile(rf"(const\s+)?({_ID}(?:\s+{_ID})*?)(?:\s*(\*)\s*|\s+)({_ID})((?:\s*\[\d+\])*)")
+_FUNCTION = re.compile(rf"(const\s+char\s*\*|{_ID}(?:\s+{_ID})*?\s)\s*(dram_\w+)\s*\((.*)\)", re.S)
 
 
-class DramConvDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in
-                ("B", "D", "H", "W", "Cin", "Do", "Ho", "Wo", "Cout", "k", "stride", "pad", "dil", "flags")]
+def parse_header(text: str):
+    """The text of a dram_hip.h -> (signatures {name: (restype, argtypes)}, {name: ctypes.Structure class},
+    {name: value} of the `#define DRAM_NAME <integer>` lines).  Knows exactly the subset of C the header is written
+    in and raises ValueError with the declaration's text on anything else -- it never guesses or skips: a wrong
+    prototype calls a kernel with shifted arguments."""
+    def bad(what, decl):
+        return ValueError(f"dram_hip.h: {what}: {' '.join(decl.split())!r}")
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    named = set(re.findall(r"\b(dram_\w+)\s*\(", text))
+    consts = {}
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(DRAM_\w+)[ \t]+(\S.*?)[ \t]*$", text, re.M):
+        if not re.fullmatch(r"-?\d+|\(-?\d+\)", m[2]):
+            raise bad(f"{m[1]} is not an integer constant", m[0])
+        consts[m[1]] = int(m[2].strip("()"))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r'\A\s*extern\s+"C"\s*\{(.*)\}\s*\Z', r"\1", text, flags=re.S)
+    text = re.sub(r"\benum\s*\{[^{}]*\}\s*;", "", text)
+    types, structs, sigs = dict(_SCALARS), {}, {}
+
+    def declarator(decl, what):
+        m = _DECLARATOR.fullmatch(decl.strip())
+        if not m:
+            raise bad(f"{what}: a type and a name are required", decl)
+        const, base, ptr, name, dims = m.groups()
+        if base not in ((_POINTEES | set(structs)) if ptr else types):
+            raise bad(f"{what} {name!r}: no ctypes mapping for type {base!r}", decl)
+        ctype = (ctypes.POINTER(structs[base]) if const and base == "DramConvDesc" else c_void_p) if ptr else types[base]
+        for n in reversed(re.findall(r"\d+", dims)):
+            ctype = ctype * int(n)
+        return name, ctype, base
+
+    def handle_typedef(m):
+        types[m[1]] = c_void_p
+        return ""
+
+    def struct_typedef(m):
+        tag, body, name = m.groups()
+        if tag != name:
+            raise bad("struct tag and typedef name differ", m[0])
+        fields = []
+        for stmt in filter(str.strip, body.split(";")):
+            first, *more = stmt.split(",")                      # int32_t D, H, W, Cin;
+            fname, ctype, base = declarator(first, f"field of {name}")
+            fields.append((fname, ctype))
+            fields += [declarator(f"{base} {d}", f"field of {name}")[:2] for d in more]
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+        return ""
+
+    text = re.sub(rf"\btypedef\s+void\s*\*\s*({_ID})\s*;", handle_typedef, text)
+    text = re.sub(rf"\btypedef\s+struct\s+({_ID})\s*\{{([^{{}}]*)\}}\s*({_ID})\s*;", struct_typedef, text)
+    *decls, rest = text.split(";")
+    for decl in decls:
+        m = _FUNCTION.fullmatch(decl.strip())
+        if not m:
+            raise bad("not a function declaration", decl)
+        ret, name, params = m[1].strip(), m[2], m[3]
+        if not ret.endswith("*") and ret not in types:
+            raise bad(f"{name}: no ctypes mapping for return type {ret!r}", decl)
+        if name in sigs:
+            raise bad(f"{name} is declared twice", decl)
+        args = [declarator(p, f"parameter of {name}")[1] for p in ([] if params.strip() == "void" else params.split(","))]
+        if any(issubclass(a, ctypes.Array) for a in args):
+            raise bad(f"{name}: array parameter", decl)
+        sigs[name] = (ctypes.c_char_p if ret.endswith("*") else types[ret], args)
+    if rest.strip():
+        raise bad("text after the last declaration", rest)
+    if named != set(sigs):
+        raise ValueError(f"dram_hip.h: `dram_...(` without a declaration of that name: {sorted(named - set(sigs))}")
+    return sigs, structs, consts
 
 
-class DramTensorRef(ctypes.Structure):
-    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", ctypes.c_int64)]
-
-
-class DramAugment(ctypes.Structure):
-    _fields_ = [("flags", ctypes.c_int32), ("n_boxes", ctypes.c_int32), ("boxes", (ctypes.c_int32 * 6) * 10),
-                ("flip_axes", ctypes.c_int32), ("sigma", c_float), ("box_lo", c_float * 3), ("box_hi", c_float * 3)]
-
-
-class DramProfRecord(ctypes.Structure):
-    _fields_ = [("family", ctypes.c_int32), ("variant", ctypes.c_int32), ("mfma_flops", c_double),
-                ("alg_flops", c_double), ("hbm_bytes", c_double), ("ms", c_float), ("pad_", c_float)]
-
-
-class DramChunkRef(ctypes.Structure):
-    _fields_ = [("tensor", ctypes.c_int32), ("pad", ctypes.c_int32), ("offset", ctypes.c_int64)]
-
-
-class DramPackRef(ctypes.Structure):
-    _fields_ = [("w", ctypes.c_void_p), ("off_f", ctypes.c_int64), ("off_b", ctypes.c_int64), ("Cout", ctypes.c_int32),
-                ("Cin", ctypes.c_int32), ("taps", ctypes.c_int32), ("pad", ctypes.c_int32)]
-
-
-DP = ctypes.POINTER(DramConvDesc)
-
-# name -> (restype, argtypes); mirrors include/dram_hip.h one to one
-SIGNATURES = {
-    "dram_version": (I, []),
-    "dram_build_info": (c_char_p, []),
-    "dram_abi_hash": (c_char_p, []),
-    "dram_stream_capture_id": (ctypes.c_ulonglong, [P]),
-    "dram_profile_family_name": (c_char_p, [I]),
-    "dram_profile_family_is_mfma": (I, [I]),
-    "dram_profile_start": (I, [I]),
-    "dram_profile_stop": (I, []),
-    "dram_profile_dropped": (I, []),
-    "dram_profile_read": (I, [P, I]),
-    "dram_pack_conv_weight": (I, [P, P, P, I, I, I, P]),
-    "dram_conv3d_fwd": (I, [P, P, P, P, P, DP, P]),
-    "dram_conv3d_bwd_data": (I, [P, P, P, P, P, DP, P]),
-    "dram_conv3d_bwd_weight_workspace": (SZ, [DP]),
-    "dram_conv3d_bwd_weight": (I, [P, P, P, DP, P, SZ, P]),
-    "dram_conv_num_mtiles": (I, [DP]),
-    "dram_conv_algo": (I, [DP]),
-    "dram_conv1x1_applicable": (I, [DP]),
-    "dram_conv1x1_num_stat_rows": (I, [DP]),
-    "dram_conv1x1_fwd": (I, [P, P, P, P, P, DP, P]),
-    "dram_conv1x1_bwd_data": (I, [P, P, P, P, P, DP, P]),
-    "dram_conv1x1_bwd_weight_workspace": (SZ, [DP]),
-    "dram_conv1x1_bwd_weight": (I, [P, P, P, DP, P, SZ, P]),
-    "dram_wgrad_w2d_applicable": (I, [DP]),
-    "dram_wgrad_w2d_workspace": (SZ, [DP]),
-    "dram_wgrad_w2d": (I, [P, P, P, DP, P, SZ, P]),
-    "dram_wino2d_applicable": (I, [DP]),
-    "dram_wino2d_num_stat_rows": (I, [DP]),
-    "dram_wino2d_pack_weight": (I, [P, P, P, I, I, P]),
-    "dram_wino2d_conv3d_fwd": (I, [P, P, P, P, P, DP, P]),
-    "dram_wino2d_conv3d_bwd_data": (I, [P, P, P, P, P, DP, P]),
-    "dram_wino_applicable": (I, [DP]),
-    "dram_conv_wgrad_algo": (I, [DP]),
-    "dram_wino_num_points": (I, [DP]),
-    "dram_wino_num_points_bwd": (I, [DP]),
-    "dram_wino_pack_weight": (I, [P, P, P, DP, P]),
-    "dram_wino_workspace": (SZ, [DP, I]),
-    "dram_wino_num_stat_rows": (I, [DP]),
-    "dram_wino_v_elems": (SZ, [DP]),
-    "dram_wino_conv3d_fwd": (I, [P, P, P, P, P, P, DP, P, SZ, P]),
-    "dram_wino_prologue_supported": (I, [DP]),
-    "dram_wino_conv3d_fwd_cat": (I, [P, I, P, I, P, P, P, P, P, DP, P, SZ, P]),
-    "dram_wino_conv3d_fwd_bn": (I, [P, P, P, P, P, P, P, P, DP, P, SZ, P]),
-    "dram_wino_conv3d_bwd_data": (I, [P, P, P, P, P, DP, P, SZ, P]),
-    "dram_wino_num_stat_rows_bwd": (I, [DP]),
-    "dram_wino_conv3d_bwd_data_bn": (I, [P, P, P, P, P, P, P, P, P, DP, P, SZ, P]),
-    "dram_wino_conv3d_bwd_weight": (I, [P, P, P, P, DP, P, SZ, P]),
-    "dram_stem_num_tiles": (I, [I, I, I, I]),
-    "dram_stem_fwd": (I, [P, P, P, P, I, I, I, I, P]),
-    "dram_stem_bwd_weight_workspace": (SZ, [I, I, I, I]),
-    "dram_stem_bwd_weight": (I, [P, P, P, I, I, I, I, P, SZ, P]),
-    "dram_stem_bwd_data_workspace": (SZ, [I, I, I, I]),
-    "dram_stem_bwd_data": (I, [P, P, P, I, I, I, I, P, SZ, P]),
-    "dram_reduce_partials_stages": (I, [I]),
-    "dram_reduce_partials": (I, [P, P, P, I, I, I, D, I, P]),
-    "dram_fold_partials_stages": (I, [I]),
-    "dram_fold_partials": (I, [P, P, P, P, P, I, I, I, D, I, P]),
-    "dram_bn_fold_finalize": (I, [P, P, P, I, I, D, P, P, P, P, F, F, I, P, P, P, P, P]),
-    "dram_bn_finalize": (I, [P, D, P, P, P, P, P, F, F, I, P, P, P, P, I, P]),
-    "dram_bn_apply": (I, [P, P, P, P, I, I, I, I, I, P, I, I, I, I, I, I, P]),
-    "dram_colsum_nparts": (I, [LL, I]),
-    "dram_bn_bwd_reduce": (I, [P, P, P, P, P, P, P, P, LL, I, I, P]),
-    "dram_bn_bwd_apply_nparts": (I, [LL, I]),
-    "dram_bn_bwd_apply": (I, [P, P, P, P, P, P, P, P, P, D, P, P, P, LL, I, I, P]),
-    "dram_bn_bwd_apply_eval": (I, [P, P, P, P, P, P, P, LL, I, I, P]),
-    "dram_colsum": (I, [P, P, LL, I, P]),
-    "dram_maxpool_fwd": (I, [P, P, P, I, I, I, I, I, P]),
-    "dram_maxpool_bwd": (I, [P, P, P, I, P, I, I, I, I, I, P]),
-    "dram_bn_maxpool_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I, P]),
-    "dram_bn_maxpool_fwd_bf16": (I, [P, P, P, P, P, P, I, I, I, I, I, P]),
-    "dram_upcat_fwd": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),
-    "dram_upcat_bwd": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),
-    "dram_upmix_stat_rows": (I, [LL]),
-    "dram_upmix_axis_fwd": (I, [P, I, P, LL, I, I, I, P]),
-    "dram_upmix_axis_fwd_final": (I, [P, P, P, I, P, LL, I, I, I, P]),
-    "dram_upmix_axis_bwd": (I, [P, I, P, I, LL, I, I, I, P]),
-    "dram_upmix_split_weight": (I, [P, P, P, I, I, I, P]),
-    "dram_upmix_merge_wgrad": (I, [P, P, P, I, I, I, P]),
-    "dram_head_nblk": (I, [LL]),
-    "dram_head_fwd": (I, [P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, P]),
-    "dram_head_bwd_nparts": (I, [LL]),
-    "dram_head_bwd": (I, [P, P, P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, P]),
-    # bf16 storage path (same argument lists as the fp32 namesakes; activation tensors are bf16)
-    "dram_pack_conv_weight_bf16_multi": (I, [P, P, I, P, D, P]),
-    "dram_pack_conv_weight_bf16_tiles": (LL, [I, I, I]),
-    "dram_cast_f32_to_bf16": (I, [P, P, LL, P]),
-    "dram_cast_bf16_to_f32": (I, [P, P, LL, P]),
-    "dram_s2d_bf16": (I, [P, P, I, I, I, I, I, P]),
-    "dram_d2s_bf16": (I, [P, P, P, P, I, I, I, I, I, P]),
-    "dram_s2_embed_weight": (I, [P, P, I, I, P]),
-    "dram_s2_extract_wgrad": (I, [P, P, I, I, P]),
-    "dram_conv_bf16_supported": (I, [DP]),
-    "dram_conv_bf16_num_stat_rows": (I, [DP]),
-    "dram_pack_conv_weight_bf16": (I, [P, P, P, I, I, I, P]),
-    "dram_conv3d_fwd_bf16": (I, [P, P, P, P, P, DP, P]),
-    "dram_conv3d_bwd_data_bf16": (I, [P, P, P, P, P, DP, P]),
-    "dram_conv3d_bwd_weight_bf16_workspace": (SZ, [DP]),
-    "dram_conv3d_bwd_weight_bf16": (I, [P, P, P, DP, P, SZ, P]),
-    "dram_stem_fwd_bf16": (I, [P, P, P, P, I, I, I, I, P]),
-    "dram_stem_bwd_weight_bf16": (I, [P, P, P, I, I, I, I, P, SZ, P]),
-    "dram_stem_bwd_data_bf16": (I, [P, P, P, I, I, I, I, P, SZ, P]),
-    "dram_stem_fwd_bf16mm": (I, [P, P, P, P, I, I, I, I, P]),
-    "dram_stem_bwd_weight_bf16mm": (I, [P, P, P, I, I, I, I, P, SZ, P]),
-    "dram_bn_apply_bf16": (I, [P, P, P, P, I, I, I, I, I, P, I, I, I, I, I, I, P]),
-    "dram_bn_bwd_reduce_bf16": (I, [P, P, P, P, P, P, P, P, LL, I, I, P]),
-    "dram_bn_bwd_apply_bf16": (I, [P, P, P, P, P, P, P, P, P, D, P, P, P, LL, I, I, P]),
-    "dram_bn_bwd_apply_eval_bf16": (I, [P, P, P, P, P, P, P, LL, I, I, P]),
-    "dram_colsum_bf16": (I, [P, P, LL, I, P]),
-    "dram_maxpool_fwd_bf16": (I, [P, P, P, I, I, I, I, I, P]),
-    "dram_maxpool_bwd_bf16": (I, [P, P, P, I, P, I, I, I, I, I, P]),
-    "dram_upcat_fwd_bf16": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),
-    "dram_upcat_bwd_bf16": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),
-    "dram_head_fwd_bf16": (I, [P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, P]),
-    "dram_head_bwd_bf16": (I, [P, P, P, P, P, P, I, I, I, P, P, I, I, I, I, I, I, P]),
-    "dram_segloss_nblk": (I, [LL]),
-    "dram_segloss_fwd": (I, [P, P, P, P, P, I, I, I, P, I, I, I, I, F, P]),
-    "dram_segloss_bwd": (I, [P, P, P, P, P, I, I, I, P, P, P, I, I, I, I, F, P]),
-    "dram_regloss_tail": (I, [P, I, P, P, P, P, P, P, P, I, P, I, I, D, D, D, D, P, P, P, P]),
-    "dram_upproject_nblk": (I, [LL]),
-    "dram_upproject": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
-    "dram_adam_multi": (I, [P, P, I, F, F, F, F, F, F, F, F, P]),
-    "dram_adam_multi_dev": (I, [P, P, I, P, P]),
-    "dram_sgd_multi": (I, [P, P, I, F, F, F, I, F, P]),
-    "dram_window_stats_nblk": (I, [LL]),
-    "dram_window_stats": (I, [P, P, LL, F, F, P]),
-    "dram_prep_image": (I, [P, P, P, P, I, I, I, I, I, I, F, F, P]),
-    "dram_prep_mask": (I, [P, P, P, I, I, I, I, I, I, P]),
-    "dram_add": (I, [P, P, P, LL, P]),
-    "dram_resample_paste": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
-    "dram_minmax_nblk": (I, [LL]),
-    "dram_minmax": (I, [P, P, LL, P]),
-    "dram_augment_image": (I, [P, P, P, P, I, I, I, P, P]),
-    "dram_augment_mask": (I, [P, P, I, I, I, P, P]),
-}
-
-OPT_CHUNK = 16384
-ABI_VERSION = 7
+with open(os.path.join(_build.INCLUDE, "dram_hip.h")) as _f:
+    SIGNATURES, _STRUCTS, _CONSTANTS = parse_header(_f.read())
+# the header's structs (DramConvDesc, DramTensorRef, DramChunkRef, DramPackRef, DramProfRecord, DramAugment) and integer
+# constants (DRAM_ERR_*, DRAM_CONV_*, DRAM_FOLD_TICKET_DOUBLES, ...) under their C names
+globals().update(_STRUCTS)
+globals().update(_CONSTANTS)
+ABI_VERSION = _CONSTANTS["DRAM_ABI_VERSION"]
+OPT_CHUNK = _CONSTANTS["DRAM_OPT_CHUNK"]
 _LIB = None
 
 
@@ -197,8 +120,8 @@ def lib_path() -> str:
 def load(build: bool = True) -> ctypes.CDLL:
     """Load libdram_hip.so.  With hipcc present the (content-hash incremental) build runs first,
     so a library older than the sources is never loaded; either way the library must carry the
-    fingerprint of THIS include/dram_hip.h -- a stale build would be called with shifted
-    arguments (wild device writes), so it is refused."""
+    fingerprint of THIS include/dram_hip.h, the file SIGNATURES was parsed from -- a build from
+    another header would be called with shifted arguments (wild device writes), so it is refused."""
     global _LIB
     if _LIB is not None:
         return _LIB

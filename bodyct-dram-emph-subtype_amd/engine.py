@@ -72,7 +72,7 @@ class Engine:
         self.e = EXPANSION[self.kind]
         # plan hint (include/dram_hip.h DRAM_CONV_ROUNDING_TOLERANT): the BasicBlock networks hand a layer's rounding
         # error on with little amplification, so the cheaper convolution estimate may win on every layer
-        self.tol = 1 if self.kind == "basic" else 0
+        self.tol = ops._lib.DRAM_CONV_ROUNDING_TOLERANT if self.kind == "basic" else 0
         self._conv_lists: Dict[tuple, list] = {}     # input shape -> [(weight name, geometry)] of a forward
         self._inflight: List[torch.cuda.Event] = []  # end-of-backward events of the steps the host has issued
         self.throttle_wait_s = 0.0                   # host time spent waiting in _throttle (bench.py reports it)

@@ -277,7 +277,7 @@ class ConvGeom:
     stride: int
     pad: int
     dil: int
-    tol: int = 0        # DRAM_CONV_ROUNDING_TOLERANT (include/dram_hip.h): plan hint set by the engine for BasicBlock networks
+    tol: int = 0        # 0 or _lib.DRAM_CONV_ROUNDING_TOLERANT: plan hint set by the engine for BasicBlock networks
 
     def out(self, n: int) -> int:
         return (n + 2 * self.pad - (self.dil * (self.k - 1) + 1)) // self.stride + 1
@@ -401,7 +401,7 @@ class ConvPlan:
         # the same geometry with DRAM_CONV_BWD_OVERLAPPED (include/dram_hip.h): a data gradient launched while another
         # stream runs weight-gradient kernels (conv3d_bwd_data(..., overlapped=True))
         self.desc_ovl = g.desc()
-        self.desc_ovl.flags |= 2
+        self.desc_ovl.flags |= _lib.DRAM_CONV_BWD_OVERLAPPED
         self.dref_ovl = ctypes.byref(self.desc_ovl)
         self.algo = int(L.dram_conv_algo(d))
         self.walgo = int(L.dram_conv_wgrad_algo(d))
@@ -533,9 +533,7 @@ def pack_conv_weights_bf16_multi(weights: List[Tensor]):
     if ent is None:
         if torch.cuda.is_current_stream_capturing():
             return None
-        tab = np.zeros(len(weights), dtype=np.dtype([("w", "<u8"), ("off_f", "<i8"), ("off_b", "<i8"), ("Cout", "<i4"),
-                                                     ("Cin", "<i4"), ("taps", "<i4"), ("pad", "<i4")]))
-        assert tab.dtype.itemsize == ctypes.sizeof(_lib.DramPackRef)
+        tab = np.zeros(len(weights), dtype=np.dtype(_lib.DramPackRef))
         chunks, layout, off = [], [], 0
         for i, w in enumerate(weights):
             _req(w, "w")
@@ -549,7 +547,7 @@ def pack_conv_weights_bf16_multi(weights: List[Tensor]):
             ntiles = _L().dram_pack_conv_weight_bf16_tiles(Cout, Cin, taps)
             _chk(min(ntiles, 0), "dram_pack_conv_weight_bf16_tiles")
             chunks.extend((i, 0, t) for t in range(ntiles))
-        ch = np.array(chunks, dtype=np.dtype([("tensor", "<i4"), ("pad", "<i4"), ("offset", "<i8")]))
+        ch = np.array(chunks, dtype=np.dtype(_lib.DramChunkRef))
         dev = weights[0].device
         ent = (torch.from_numpy(tab.view(np.uint8).copy()).to(dev), torch.from_numpy(ch.view(np.uint8).copy()).to(dev),
                len(chunks), off, layout)
@@ -892,7 +890,7 @@ def stem_bwd_data(dy: Tensor, w: Tensor, in_shape) -> Tensor:
 
 
 # --------------------------------------------------------------------------- batch norm
-FOLD_TICKET_DOUBLES = 256       # include/dram_hip.h DRAM_FOLD_TICKET_DOUBLES: per-call ticket words behind the stage rows
+FOLD_TICKET_DOUBLES = _lib.DRAM_FOLD_TICKET_DOUBLES     # per-call ticket words behind the stage rows
 
 
 def reduce_partials(partial: Tensor, tail: Optional[float] = None, want_f32: bool = False):

@@ -9,7 +9,6 @@ arguments the reference keeps, train.py:25,27): ``torch.optim.Optimizer`` subcla
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List
 
 import numpy as np
@@ -17,10 +16,8 @@ import torch
 
 from . import _lib, ops
 
-_TABLE_DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8")])
-_CHUNK_DT = np.dtype([("tensor", "<i4"), ("pad", "<i4"), ("offset", "<i8")])
-assert _TABLE_DT.itemsize == ctypes.sizeof(_lib.DramTensorRef)
-assert _CHUNK_DT.itemsize == ctypes.sizeof(_lib.DramChunkRef)
+_TABLE_DT = np.dtype(_lib.DramTensorRef)
+_CHUNK_DT = np.dtype(_lib.DramChunkRef)
 
 
 def build_chunks(sizes, chunk: int = _lib.OPT_CHUNK):

@@ -21,6 +21,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
     assert declared <= exported, declared - exported
+    assert len(_lib.SIGNATURES) == len(declared & exported)
     lib = _lib.load()                       # dlopen works without a GPU; no compute call is made
     assert lib.dram_version() == _lib.ABI_VERSION
     assert lib.dram_abi_hash().decode() == _build.abi_hash()
@@ -33,6 +34,84 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert lib.dram_conv_num_mtiles(ctypes.byref(bad)) == -1            # inconsistent output dims rejected
     assert lib.dram_stem_num_tiles(2, 64, 128, 128) == 2 * 16 * 16 * 16
     assert ctypes.sizeof(_lib.DramTensorRef) == 40 and ctypes.sizeof(_lib.DramChunkRef) == 16
+
+
+def test_binding_is_parsed_from_the_header():
+    """_lib reads prototypes, structs and constants from include/dram_hip.h: one declaration of each kind against
+    expectations written here by hand, the struct layouts as the C compiler lays them out, and the constants."""
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_ulonglong, c_void_p, sizeof
+    from bodyct_dram_emph_subtype_amd import _lib
+    P, I, LL, F, D, SZ, DP = c_void_p, c_int, c_longlong, c_float, c_double, c_size_t, POINTER(_lib.DramConvDesc)
+    expect = {
+        "dram_version": (I, []),
+        "dram_abi_hash": (c_char_p, []),
+        "dram_build_info": (c_char_p, []),
+        "dram_profile_family_name": (c_char_p, [I]),
+        "dram_stream_capture_id": (c_ulonglong, [P]),
+        "dram_conv3d_bwd_weight": (I, [P, P, P, DP, P, SZ, P]),
+        "dram_wino_workspace": (SZ, [DP, I]),
+        "dram_colsum_nparts": (I, [LL, I]),
+        "dram_pack_conv_weight_bf16_tiles": (LL, [I, I, I]),
+        "dram_bn_bwd_apply": (I, [P, P, P, P, P, P, P, P, P, D, P, P, P, LL, I, I, P]),
+        "dram_bn_bwd_apply_eval_bf16": (I, [P, P, P, P, P, P, P, LL, I, I, P]),
+        "dram_adam_multi": (I, [P, P, I, F, F, F, F, F, F, F, F, P]),
+        "dram_maxpool_fwd": (I, [P, P, P, I, I, I, I, I, P]),
+        "dram_profile_read": (I, [P, I]),
+        "dram_regloss_tail": (I, [P, I, P, P, P, P, P, P, P, I, P, I, I, D, D, D, D, P, P, P, P]),
+        "dram_augment_mask": (I, [P, P, I, I, I, P, P]),
+    }
+    for name, (res, args) in expect.items():
+        got_res, got_args = _lib.SIGNATURES[name]
+        assert got_res is res and list(got_args) == args, (name, got_res, got_args)
+
+    sizes = {"DramConvDesc": 56, "DramTensorRef": 40, "DramChunkRef": 16, "DramPackRef": 40, "DramProfRecord": 40,
+             "DramAugment": 280}
+    assert {n: sizeof(getattr(_lib, n)) for n in sizes} == sizes
+    assert [f for f, _ in _lib.DramConvDesc._fields_] == ["B", "D", "H", "W", "Cin", "Do", "Ho", "Wo", "Cout", "k", "stride",
+                                                          "pad", "dil", "flags"]
+    assert [f for f, _ in _lib.DramPackRef._fields_] == ["w", "off_f", "off_b", "Cout", "Cin", "taps", "pad"]
+    assert (_lib.DramAugment.boxes.offset, _lib.DramAugment.flip_axes.offset, _lib.DramAugment.box_hi.offset) == (8, 248, 268)
+    assert (_lib.DramProfRecord.mfma_flops.offset, _lib.DramProfRecord.ms.offset) == (8, 32)
+    a = _lib.DramAugment()
+    assert len(a.boxes) == 10 and len(a.boxes[0]) == 6 and len(a.box_lo) == 3
+    dt = np.dtype(_lib.DramTensorRef)
+    assert dt.names == ("p", "g", "m", "v", "n") and dt.itemsize == 40
+    assert [dt.fields[n][1] for n in dt.names] == [0, 8, 16, 24, 32] and dt["p"] == np.dtype("<u8") and dt["n"] == np.dtype("<i8")
+    assert np.dtype(_lib.DramChunkRef) == np.dtype([("tensor", "<i4"), ("pad", "<i4"), ("offset", "<i8")])
+
+    assert (_lib.ABI_VERSION, _lib.OPT_CHUNK, _lib.DRAM_FOLD_TICKET_DOUBLES) == (7, 16384, 256)
+    assert (_lib.DRAM_CONV_BWD_OVERLAPPED, _lib.DRAM_CONV_ROUNDING_TOLERANT) == (2, 1)
+    assert (_lib.DRAM_OK, _lib.DRAM_ERR_BAD_ARG, _lib.DRAM_ERR_UNSUPPORTED, _lib.DRAM_ERR_WORKSPACE) == (0, -1, -2, -3)
+
+
+def test_header_parser_refuses_what_it_does_not_understand():
+    """A header the parser cannot fully understand must not yield a binding: every case raises, naming the culprit."""
+    from bodyct_dram_emph_subtype_amd import _lib
+    pre = "typedef void* dram_stream_t;\n"
+    sigs, structs, consts = _lib.parse_header(
+        pre + "#define DRAM_N (-3)\n/* int dram_no(int a); */\ntypedef struct S { const float* p; int32_t a, b[2][3]; } S;\n"
+        "int dram_ok(const S* s, long long n,\n            dram_stream_t stream);\nsize_t dram_sz(void);\n")
+    assert sigs == {"dram_ok": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
+                    "dram_sz": (ctypes.c_size_t, [])}
+    assert consts == {"DRAM_N": -3} and ctypes.sizeof(structs["S"]) == 40 and structs["S"].b.offset == 12
+    for text, culprit in [
+            (pre + "int dram_x(short a, dram_stream_t s);", "short"),               # unknown parameter type
+            ("int dram_x(int a, dram_stream_t s);", "dram_stream_t"),              # ... a typedef the text does not have
+            (pre + "int dram_x(int, dram_stream_t s);", "dram_x"),                  # unnamed parameters
+            (pre + "int dram_x(const float*, dram_stream_t s);", "dram_x"),
+            (pre + "int dram_x(long long, int b);", "dram_x"),
+            ("typedef struct T { short a; } T;", "short"),                          # unknown field type
+            ("typedef struct T { int32_t a; } U;", "T"),
+            ("short dram_x(int a);", "dram_x"),                                     # unknown return type
+            ("float* dram_x(int a);", "dram_x"),
+            ("int dram_x(int a)\nint dram_y(void);", "dram_x"),                     # half-matched declarations
+            ("int dram_x(int a); int dram_y(int b) { return b; }", "dram_y"),
+            ("int dram_x(int a[3]);", "dram_x"),
+            ("int dram_x(int a); int dram_x(int a);", "dram_x"),
+            ("#define dram_m(a) dram_x(a)\nint dram_x(int a);", "dram_m"),          # a dram_...( that is no entry point
+            ("#define DRAM_K (1 << 4)\n", "DRAM_K")]:                               # not a plain integer
+        with pytest.raises(ValueError, match=culprit):
+            _lib.parse_header(text)
 
 
 def test_conv_plan_is_host_side_and_consistent(monkeypatch):
