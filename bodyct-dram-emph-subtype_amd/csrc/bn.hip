@@ -198,46 +198,12 @@ __global__ void bn_apply_kernel(const T* __restrict__ y, const float* __restrict
   }
 }
 
-// The same pass for channel counts whose quad count divides the block size (every network width but 576): a
-// thread's channel quad is then fixed across its grid-stride loop (no 64-bit modulo, scale / shift in registers),
-// and U independent 16-byte (bf16: 8-byte) loads per tensor are issued before the first use -- the plain loop has
-// one load per thread in flight, ~8 MB chip-wide, less than the HBM latency-bandwidth product.
-template <int RES, typename T, int U>
-__global__ __launch_bounds__(256) void bn_apply_fast_kernel(const T* __restrict__ y, const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, const T* __restrict__ res,
-                                                            T* __restrict__ z, int Q, long total4, int relu) {
-  const int q = threadIdx.x % Q;
-  const float4 sc = *reinterpret_cast<const float4*>(scale + 4 * q);
-  const float4 sh = *reinterpret_cast<const float4*>(shift + 4 * q);
-  const long stride = (long)gridDim.x * 256;
-  for (long i0 = blockIdx.x * 256L + threadIdx.x; i0 < total4; i0 += U * stride) {
-    float4 v[U], rr[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long i = i0 + u * stride;
-      if (i < total4) {
-        v[u] = ld4<T>(y, 4 * i);
-        if (RES == 1) rr[u] = ld4<T>(res, 4 * i);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long i = i0 + u * stride;
-      if (i < total4) {
-        float4 o;
-        o.x = __builtin_fmaf(v[u].x, sc.x, sh.x); o.y = __builtin_fmaf(v[u].y, sc.y, sh.y);
-        o.z = __builtin_fmaf(v[u].z, sc.z, sh.z); o.w = __builtin_fmaf(v[u].w, sc.w, sh.w);
-        if (RES == 1) { o.x += rr[u].x; o.y += rr[u].y; o.z += rr[u].z; o.w += rr[u].w; }
-        if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-        st4<T>(z, 4 * i, o);
-      }
-    }
-  }
-}
-
-// The same pass as ONE-SHOT blocks (common.h, ew_blocks): block b owns the 1024 channel quads [1024 b, 1024 (b + 1)),
-// four per thread 256 apart (the thread's channel quad stays fixed: 256 % Q == 0).  NT: streaming cache policy on the
-// tensor loads and stores.  Same expression per element (bit-identical results).
+// The same pass for channel counts whose quad count divides the block size (every network width but 576), as ONE-SHOT
+// blocks (common.h, ew_blocks): block b owns the 1024 channel quads [1024 b, 1024 (b + 1)), four per thread 256 apart.
+// The thread's channel quad is fixed (256 % Q == 0: no 64-bit modulo, scale / shift in registers), and its four
+// independent 16-byte (bf16: 8-byte) loads per tensor are issued before the first use -- the plain loop has one load
+// per thread in flight, ~8 MB chip-wide, less than the HBM latency-bandwidth product.  NT: streaming cache policy on
+// the tensor loads and stores.  Same expression per element (bit-identical results).
 template <int RES, typename T, bool NT>
 __global__ __launch_bounds__(256) void bn_apply_shot_kernel(const T* __restrict__ y, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, const T* __restrict__ res,
@@ -460,12 +426,12 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dz, const T* __restric
 // per-channel constants (mean, invstd, gamma, the two batch means -- double multiplies in the generic kernel, per
 // element) live in registers, there is no 64-bit modulo per element, and two elements are in flight per thread.
 // Same expression per element as bn_bwd_apply_kernel (bit-identical results).
-// SHOT 0: capped grid + grid-stride loop; SHOT 1 / 2: one-shot blocks of 256 U K quads (common.h, ew_blocks), 2 =
-// streaming loads and stores.  Per-block column sums of dy (the bias gradient of a convolution in front) need few
-// enough blocks for the partial rows: those launches sweep K > 1 consecutive 256 U-quad pieces per block (4,096 quads:
-// 5.3 TB/s in tools/stream_probe.hip's three-stream form against 5.7 for K = 1 and 4.1-4.6 for the capped grid).  U elements in flight per thread: 2 for fp32, 4 for bf16 (half the bytes per element against the same
-// per-thread set-up of the channel constants).
-template <typename T, int SHOT, int U, int K>
+// One-shot blocks of 256 U K quads (common.h, ew_blocks); NT: streaming loads and stores.  Per-block column sums of dy
+// (the bias gradient of a convolution in front) need few enough blocks for the partial rows: those launches sweep
+// K > 1 consecutive 256 U-quad pieces per block (4,096 quads: 5.3 TB/s in tools/stream_probe.hip's three-stream form
+// against 5.7 for K = 1 and 4.1-4.6 for a capped grid with a grid-stride loop).  U elements in flight per thread: 2 for
+// fp32, 4 for bf16 (half the bytes per element against the same per-thread set-up of the channel constants).
+template <typename T, bool NT, int U, int K>
 __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(const T* __restrict__ dz, const T* __restrict__ z,
                                                                 const T* __restrict__ y, const float* __restrict__ mean,
                                                                 const float* __restrict__ invstd,
@@ -492,17 +458,17 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(const T* __restr
   const float4 mgx = make_float4((float)(sums[C + c] * inv_count), (float)(sums[C + c + 1] * inv_count),
                                  (float)(sums[C + c + 2] * inv_count), (float)(sums[C + c + 3] * inv_count));
   float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
-  const long stride = SHOT ? 256L : (long)gridDim.x * 256;
+  constexpr long stride = 256L;
   int kk = 0;
-  for (long i0 = blockIdx.x * (SHOT ? 256L * U * K : 256L) + threadIdx.x; i0 < total4; i0 += U * stride) {
+  for (long i0 = blockIdx.x * (256L * U * K) + threadIdx.x; i0 < total4; i0 += U * stride) {
     float4 g[U], yv[U], zv[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long i = i0 + u * stride;
       if (i < total4) {
-        g[u] = SHOT == 2 ? ld4s<T>(dz, 4 * i) : ld4<T>(dz, 4 * i);
-        yv[u] = SHOT == 2 ? ld4s<T>(y, 4 * i) : ld4<T>(y, 4 * i);
-        if (relu && z) zv[u] = SHOT == 2 ? ld4s<T>(z, 4 * i) : ld4<T>(z, 4 * i);
+        g[u] = NT ? ld4s<T>(dz, 4 * i) : ld4<T>(dz, 4 * i);
+        yv[u] = NT ? ld4s<T>(y, 4 * i) : ld4<T>(y, 4 * i);
+        if (relu && z) zv[u] = NT ? ld4s<T>(z, 4 * i) : ld4<T>(z, 4 * i);
       }
     }
 #pragma unroll
@@ -522,13 +488,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(const T* __restr
         o.y = ga.y * is.y * (gg.y - mg.y - ((yv[u].y - mu.y) * is.y) * mgx.y);
         o.z = ga.z * is.z * (gg.z - mg.z - ((yv[u].z - mu.z) * is.z) * mgx.z);
         o.w = ga.w * is.w * (gg.w - mg.w - ((yv[u].w - mu.w) * is.w) * mgx.w);
-        if (SHOT == 2) st4s<T>(dy, 4 * i, o); else st4<T>(dy, 4 * i, o);
+        if (NT) st4s<T>(dy, 4 * i, o); else st4<T>(dy, 4 * i, o);
         cs.x += o.x; cs.y += o.y; cs.z += o.z; cs.w += o.w;
       }
     }
-    if (SHOT && ++kk == K) break;
+    if (++kk == K) break;
   }
-  if ((SHOT == 0 || K > 1) && colpart) {
+  if (K > 1 && colpart) {
     __shared__ float4 sm[256];
     sm[threadIdx.x] = cs;
     __syncthreads();
@@ -545,49 +511,48 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(const T* __restr
 
 // BatchNorm backward on the RUNNING statistics (eval mode): dy = scale * dz * mask -- no batch-mean terms, so no
 // dependence on a reduction.  The mask is read from z (y is then never touched) or re-derived from y with the forward's
-// fma.  Block b sweeps `per` consecutive quads (one-shot blocks: per = 4,096, grid = ceil(total4 / per); capped grid:
-// per = 256 and a grid-stride loop), four quads in flight per thread; with 256 % (C / 4) == 0 the thread's channel quad
-// is fixed and its column sums of dy (the bias gradient of a convolution in front) are folded per block in a fixed order.
+// fma.  One-shot blocks: block b sweeps the 4,096 consecutive quads [4096 b, 4096 (b + 1)) (grid = ceil(total4 / 4096)),
+// four quads in flight per thread; with 256 % (C / 4) == 0 the thread's channel quad is fixed and its column sums of dy
+// (the bias gradient of a convolution in front) are folded per block in a fixed order.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_eval_kernel(const T* __restrict__ dz, const T* __restrict__ z,
                                                                 const T* __restrict__ y, const float* __restrict__ scale,
                                                                 const float* __restrict__ shift, T* __restrict__ dy, int C,
-                                                                long total4, int relu, int per,
-                                                                float* __restrict__ colpart) {
+                                                                long total4, int relu, float* __restrict__ colpart) {
   const int Q = C >> 2;
   float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (long base = blockIdx.x * (long)per; base < total4; base += (long)gridDim.x * per) {
-    for (int j0 = 0; j0 < per; j0 += 1024) {
-      float4 g[4], m[4];
+  const long base = blockIdx.x * 4096L;
+#pragma unroll 1
+  for (int j0 = 0; j0 < 4096; j0 += 1024) {
+    float4 g[4], m[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const long i = base + j0 + 256 * u + threadIdx.x;
-        if (j0 + 256 * u < per && i < total4) {
-          g[u] = ld4<T>(dz, 4 * i);
-          if (relu) m[u] = z ? ld4<T>(z, 4 * i) : ld4<T>(y, 4 * i);
-        }
+    for (int u = 0; u < 4; ++u) {
+      const long i = base + j0 + 256 * u + threadIdx.x;
+      if (i < total4) {
+        g[u] = ld4<T>(dz, 4 * i);
+        if (relu) m[u] = z ? ld4<T>(z, 4 * i) : ld4<T>(y, 4 * i);
       }
+    }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const long i = base + j0 + 256 * u + threadIdx.x;
-        if (j0 + 256 * u < per && i < total4) {
-          const int c = 4 * (int)(i % Q);
-          const float4 sc = *reinterpret_cast<const float4*>(scale + c);
-          float4 gg = g[u];
-          if (relu) {
-            float4 zv = m[u];
-            if (!z) {
-              const float4 sh = *reinterpret_cast<const float4*>(shift + c);
-              zv = make_float4(__builtin_fmaf(zv.x, sc.x, sh.x), __builtin_fmaf(zv.y, sc.y, sh.y),
-                               __builtin_fmaf(zv.z, sc.z, sh.z), __builtin_fmaf(zv.w, sc.w, sh.w));
-            }
-            gg.x = zv.x > 0.f ? gg.x : 0.f; gg.y = zv.y > 0.f ? gg.y : 0.f;
-            gg.z = zv.z > 0.f ? gg.z : 0.f; gg.w = zv.w > 0.f ? gg.w : 0.f;
+    for (int u = 0; u < 4; ++u) {
+      const long i = base + j0 + 256 * u + threadIdx.x;
+      if (i < total4) {
+        const int c = 4 * (int)(i % Q);
+        const float4 sc = *reinterpret_cast<const float4*>(scale + c);
+        float4 gg = g[u];
+        if (relu) {
+          float4 zv = m[u];
+          if (!z) {
+            const float4 sh = *reinterpret_cast<const float4*>(shift + c);
+            zv = make_float4(__builtin_fmaf(zv.x, sc.x, sh.x), __builtin_fmaf(zv.y, sc.y, sh.y),
+                             __builtin_fmaf(zv.z, sc.z, sh.z), __builtin_fmaf(zv.w, sc.w, sh.w));
           }
-          const float4 o = make_float4(sc.x * gg.x, sc.y * gg.y, sc.z * gg.z, sc.w * gg.w);
-          st4<T>(dy, 4 * i, o);
-          cs.x += o.x; cs.y += o.y; cs.z += o.z; cs.w += o.w;
+          gg.x = zv.x > 0.f ? gg.x : 0.f; gg.y = zv.y > 0.f ? gg.y : 0.f;
+          gg.z = zv.z > 0.f ? gg.z : 0.f; gg.w = zv.w > 0.f ? gg.w : 0.f;
         }
+        const float4 o = make_float4(sc.x * gg.x, sc.y * gg.y, sc.z * gg.z, sc.w * gg.w);
+        st4<T>(dy, 4 * i, o);
+        cs.x += o.x; cs.y += o.y; cs.z += o.z; cs.w += o.w;
       }
     }
   }
@@ -729,29 +694,20 @@ static int bn_apply_impl(const T* y, const float* scale, const float* shift, con
   if (!y || !scale || !shift || !z || B < 1 || D < 1 || H < 1 || W < 1 || C < 4 || (C & 3)) return DRAM_ERR_BAD_ARG;
   const long total4 = (long)B * D * H * W * (C >> 2);
   hipStream_t s = (hipStream_t)stream;
-  const int grid = ew_blocks(total4, 256, 4096);
+  const int grid = ew_blocks(total4, 256);
   // y read, z written, residual read (identity: full size; shortcut A: 1/rs^3 of Cr/C of it)
   const double res_frac = !residual ? 0.0 : ((double)Cr / C) / ((double)rs * rs * rs);
   DramProf prof(DRAM_FAM_BN, 2, 0.0, 4.0 * sizeof(T) * (double)total4 * (2.0 + res_frac), s);
   const int Q = C >> 2;
   const bool identity = residual && rs == 1 && Cr == C && Dr == D && Hr == H && Wr == W;
-  static const int ew_u = tune_env("DRAM_EW_U") ? atoi(tune_env("DRAM_EW_U")) : 4;      // A/B switch (tools/ew_bench.py)
-  if ((!residual || identity) && 256 % Q == 0 && ew_u > 0 && ew_shape() > 0) {
-    const int g1 = ew_blocks(total4, 1024, 0);
+  if ((!residual || identity) && 256 % Q == 0) {
+    const int g1 = ew_blocks(total4, 1024);
 #define BN_SHOT_(RES_, NT_) hipLaunchKernelGGL((bn_apply_shot_kernel<RES_, T, NT_>), dim3(g1), dim3(256), 0, s, y, scale, \
                                                shift, residual, z, Q, total4, relu)
     const bool nt = ew_stream(sizeof(T) * 4 * total4);
     if (!residual) { if (nt) BN_SHOT_(0, true); else BN_SHOT_(0, false); }
     else           { if (nt) BN_SHOT_(1, true); else BN_SHOT_(1, false); }
 #undef BN_SHOT_
-  } else if ((!residual || identity) && 256 % Q == 0 && ew_u > 0) {
-    const long per = (total4 + 255) / 256;
-    const int g2 = (int)((per + ew_u - 1) / ew_u < 8192 ? ((per + ew_u - 1) / ew_u < 1 ? 1 : (per + ew_u - 1) / ew_u) : 8192);
-#define BN_FAST_(RES_, U_) hipLaunchKernelGGL((bn_apply_fast_kernel<RES_, T, U_>), dim3(g2), dim3(256), 0, s, y, scale, shift, \
-                                              residual, z, Q, total4, relu)
-    if (!residual) { if (ew_u >= 4) BN_FAST_(0, 4); else if (ew_u >= 2) BN_FAST_(0, 2); else BN_FAST_(0, 1); }
-    else           { if (ew_u >= 4) BN_FAST_(1, 4); else if (ew_u >= 2) BN_FAST_(1, 2); else BN_FAST_(1, 1); }
-#undef BN_FAST_
   } else if (!residual) {
     hipLaunchKernelGGL((bn_apply_kernel<0, T>), dim3(grid), dim3(256), 0, s, y, scale, shift, (const T*)nullptr, 0,
                        1, z, D, H, W, C, total4, relu);
@@ -839,8 +795,7 @@ extern "C" int dram_colsum_bf16(const void* a, float* partial, long long rows, i
 extern "C" int dram_bn_bwd_apply_nparts(long long rows, int C) {
   if (rows < 1 || C < 4 || (C & 3)) return DRAM_ERR_BAD_ARG;
   if (256 % (C >> 2) != 0) return DRAM_ERR_UNSUPPORTED;
-  if (ew_shape() > 0) return ew_blocks((long)rows * (C >> 2), 4096, 0);    // one row per 4,096-quad block (fast kernel)
-  return ew_grid((long)rows * (C >> 2));
+  return ew_blocks((long)rows * (C >> 2), 4096);    // one row per 4,096-quad block (fast kernel)
 }
 
 template <typename T>
@@ -855,16 +810,15 @@ static int bn_bwd_apply_impl(const T* dz, const T* z, const T* y, const float* m
   if (colsum_partial && dram_bn_bwd_apply_nparts(rows, C) < 1) return DRAM_ERR_UNSUPPORTED;
   const long total4 = (long)rows * (C >> 2);
   DramProf prof(DRAM_FAM_BN, 5, 0.0, 4.0 * sizeof(T) * (double)total4 * (relu && z ? 4.0 : 3.0), (hipStream_t)stream);
-  if (256 % (C >> 2) == 0) {   // (with column sums: same grid as the generic kernel, one partial row per block)
-#define BN_BWD_FAST_(SHOT_, U_, K_, GRID_)                                                                                \
-  hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<T, SHOT_, U_, K_>), dim3(GRID_), dim3(256), 0, (hipStream_t)stream, dz, z, y, \
+  if (256 % (C >> 2) == 0) {
+#define BN_BWD_FAST_(NT_, U_, K_, GRID_)                                                                                 \
+  hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<T, NT_, U_, K_>), dim3(GRID_), dim3(256), 0, (hipStream_t)stream, dz, z, y, \
                      mean, invstd, gamma, sums, count_dev ? 0.0 : 1.0 / count, count_dev, dy, C, total4, relu, scale,     \
                      shift, colsum_partial)
     constexpr int U = sizeof(T) == 2 ? 4 : 2;
-    if (ew_shape() == 0) BN_BWD_FAST_(0, 2, 1, ew_grid(total4));
-    else if (colsum_partial) BN_BWD_FAST_(1, U, 16 / U, ew_blocks(total4, 4096, 0));        // = dram_bn_bwd_apply_nparts
-    else if (ew_stream(sizeof(T) * 4 * total4)) BN_BWD_FAST_(2, U, 1, ew_blocks(total4, 256 * U, 0));
-    else BN_BWD_FAST_(1, U, 1, ew_blocks(total4, 256 * U, 0));
+    if (colsum_partial) BN_BWD_FAST_(false, U, 16 / U, ew_blocks(total4, 4096));        // = dram_bn_bwd_apply_nparts
+    else if (ew_stream(sizeof(T) * 4 * total4)) BN_BWD_FAST_(true, U, 1, ew_blocks(total4, 256 * U));
+    else BN_BWD_FAST_(false, U, 1, ew_blocks(total4, 256 * U));
 #undef BN_BWD_FAST_
   }
   else
@@ -898,10 +852,8 @@ static int bn_bwd_apply_eval_impl(const T* dz, const T* z, const T* y, const flo
   const long total4 = (long)rows * (C >> 2);
   DramProf prof(DRAM_FAM_BN, 11, 0.0, 4.0 * sizeof(T) * (double)total4 * (relu ? 3.0 : 2.0), (hipStream_t)stream);
   // (the grid is what dram_bn_bwd_apply_nparts reports: one partial row per block)
-  const int per = ew_shape() == 0 ? 256 : 4096;
-  const int grid = ew_shape() == 0 ? ew_grid(total4) : ew_blocks(total4, 4096, 0);
-  hipLaunchKernelGGL((bn_bwd_apply_eval_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dz, z, y, scale, shift,
-                     dy, C, total4, relu, per, colsum_partial);
+  hipLaunchKernelGGL((bn_bwd_apply_eval_kernel<T>), dim3(ew_blocks(total4, 4096)), dim3(256), 0, (hipStream_t)stream, dz,
+                     z, y, scale, shift, dy, C, total4, relu, colsum_partial);
   DRAM_LAUNCH_CHECK();
   return DRAM_OK;
 }
@@ -921,7 +873,7 @@ extern "C" int dram_add(const float* a, const float* b, float* out, long long n,
   if (!a || !b || !out || n < 1) return DRAM_ERR_BAD_ARG;
   const long n4 = ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0) ? n / 4 : 0;
   DramProf prof(DRAM_FAM_BN, 6, 0.0, 12.0 * (double)n, (hipStream_t)stream);
-  hipLaunchKernelGGL(add_kernel, dim3(ew_blocks(n4 > 0 ? n4 : (n + 3) / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(add_kernel, dim3(ew_blocks(n4 > 0 ? n4 : (n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const float4*)a, (const float4*)b, (float4*)out, n4, a, b, out, (long)n);
   DRAM_LAUNCH_CHECK();
   return DRAM_OK;

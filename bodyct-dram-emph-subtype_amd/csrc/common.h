@@ -128,9 +128,10 @@ template <> __device__ __forceinline__ void st4s<bf16_t>(bf16_t* p, long off, fl
   __builtin_nontemporal_store(t, reinterpret_cast<u32x2_nt*>(p + off));
 }
 
-// Test / A-B switches (DRAM_CONV_ALGO, DRAM_W2D_V, DRAM_WINO_TILING, DRAM_EW_SHAPE, ...) are read from the environment
-// ONLY when DRAM_TUNING=1 is set as well (tests/conftest.py and the tools set it): a stray DRAM_* variable in a user's
-// environment cannot silently change which kernel variant the product path runs.
+// Test switches that select among live kernel forms (DRAM_CONV_ALGO, DRAM_W2D_V, DRAM_WINO_TILING, ...; the whole set
+// is the table in DESIGN.md, "Tuning switches") are read from the environment ONLY when DRAM_TUNING=1 is set as well
+// (tests/conftest.py and the tools set it): a stray DRAM_* variable in a user's environment cannot silently change
+// which kernel variant the product path runs.
 static inline const char* tune_env(const char* name) {
   static const bool on = [] { const char* t = getenv("DRAM_TUNING"); return t && t[0] == '1'; }();
   return on ? getenv(name) : nullptr;
@@ -138,21 +139,16 @@ static inline const char* tune_env(const char* name) {
 
 // Launch shape of the streaming element-wise kernels: ONE-SHOT blocks (block b owns elements [b * per, (b + 1) * per),
 // no grid-stride loop) -- the dispatcher hands blocks out in order, so the chip sweeps a narrow moving window of each
-// tensor; a capped grid with a grid-stride loop reads + writes 1 GiB at 4.6-5.0 TB/s, one-shot blocks at 6.0-6.2
-// (tools/stream_probe.hip).  DRAM_EW_SHAPE=0 restores the capped grid (A/B).
-static inline int ew_shape() {
-  static const int v = tune_env("DRAM_EW_SHAPE") ? atoi(tune_env("DRAM_EW_SHAPE")) : 2;   // 0 capped, 1 one-shot, 2 + nt
-  return v;
+// tensor; a capped grid with a grid-stride loop read + wrote 1 GiB at 4.6-5.0 TB/s, one-shot blocks at 6.0-6.2
+// (tools/stream_probe.hip).
+static inline int ew_blocks(long items, int per_block) {
+  long b = (items + per_block - 1) / per_block;
+  if (b < 1) b = 1;
+  return (int)(b > 0x7fffffffL ? 0x7fffffffL : b);
 }
 // streaming cache policy only for tensors that cannot stay in the 256 MiB Infinity Cache anyway: on a 67 MB tensor
 // (producer -> consumer inside the cache) the non-temporal forms cost 5-15 %, on a 537 MB one they gain 7-10 %
-static inline bool ew_stream(long long tensor_bytes) { return ew_shape() >= 2 && tensor_bytes >= (256LL << 20); }
-static inline int ew_blocks(long items, int per_block, int cap) {
-  long b = (items + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (ew_shape() == 0 && b > cap) b = cap;
-  return (int)(b > 0x7fffffffL ? 0x7fffffffL : b);
-}
+static inline bool ew_stream(long long tensor_bytes) { return tensor_bytes >= (256LL << 20); }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 

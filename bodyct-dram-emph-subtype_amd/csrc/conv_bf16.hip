@@ -14,10 +14,10 @@
 //                                weights stream through a 3-slot LDS ring, three taps (one kx row) per slot, two slots ahead.
 //                                Both images are XOR-swizzled in 16-B slots so that every ds_read_b128 operand fetch
 //                                is conflict-free for the four lane groups of that instruction.
-//   wgrad3_bf16_kernel           weight gradient dW[tap][co][ci] = sum_v dy[v][co] x[v + tap][ci]: the contraction runs
+//   wgrad3b_bf16_kernel          weight gradient dW[tap][co][ci] = sum_v dy[v][co] x[v + tap][ci]: the contraction runs
 //                                over VOXELS, i.e. over the row index of both NDHWC operands, so MFMA operands are
 //                                transposed LDS reads (ds_read_b64_tr_b16) of the same halo image + a dy tile.  8 waves;
-//                                wave = (32-channel half of a 64-wide co block) x (every 4th tap): 6-7 accumulators.
+//                                wave = (both 32-channel halves of a 64-wide co block) x (every 8th tap): 6-8 accumulators.
 //                                Partial sums per voxel split -> fp32 slabs -> fixed-order reduce (deterministic).
 //   pack / cast kernels          fp32 [Cout][Cin][k^3] -> bf16 wf[tap][Cout][Cin], wb[26 - tap][Cin][Cout]; f32 <-> bf16.
 //
@@ -58,8 +58,6 @@ __device__ __forceinline__ void decode_tile(int t, const CGeom& g, int& b, int& 
   lz0 = tzi * 4; ly0 = tyi * 8; lx0 = txi * 8;
 }
 
-// Ablation switch of the tuning builds (tools/conv_bf16_ablate.sh; 0 = the product): 1 no weight DMA, 2 no halo DMA,
-// 3 no LDS operand reads, 4 no MFMAs, 5 no epilogue stores, 6 no barriers.  Results are garbage in those builds.
 // "s_waitcnt vmcnt(0)" as the BUILTIN (gfx9 encoding: lgkmcnt 15, expcnt 7, vmcnt 0), not as inline asm: the wait-count
 // pass reads the builtin and knows that no LDS-DMA is outstanding behind it.  Behind an asm wait it still believed the
 // previous step's DMA pending and guarded the first operand read of every step with a wait that also covered part of
@@ -70,9 +68,6 @@ __device__ __forceinline__ void decode_tile(int t, const CGeom& g, int& b, int& 
     asm volatile("" ::: "memory");         \
   } while (0)
 
-#ifndef DRAM_BF16_ABL
-#define DRAM_BF16_ABL 0
-#endif
 constexpr int HALO_GRAN = 2560;   // 6 x 10 x 10 voxels x 4 slots = 2400 16-B granules, padded to 10 x 256
 
 // LDS-DMA through a buffer descriptor: the per-lane source is a 32-bit BYTE offset held in a register for the whole
@@ -151,14 +146,11 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3_bf16_kernel(const bf16_t* __
   }
   auto issue_halo = [&](int c) __attribute__((always_inline)) {
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(x, xbase + (long)c * 64, xbytes);
-    if (DRAM_BF16_ABL == 2) return;
 #pragma unroll
     for (int i = 0; i < HROUNDS; ++i) BUFLDS16(rs, hoff[i], halo + i * (NT * 16) + wave * 1024);
   };
   auto issue_w = [&](int c, int gi, unsigned char* buf) __attribute__((always_inline)) {
-    const __amdgpu_buffer_rsrc_t rs = DRAM_BF16_ABL == 8 ? make_rsrc(w, 0, wbytes)
-                                                          : make_rsrc(w, ((long)(3 * gi) * g.Cout * g.Cin + c * 32) * 2, wbytes);
-    if (DRAM_BF16_ABL == 1) return;
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(w, ((long)(3 * gi) * g.Cout * g.Cin + c * 32) * 2, wbytes);
 #pragma unroll
     for (int r = 0; r < WROUNDS; ++r) BUFLDS16(rs, woff[r], buf + r * (NT * 16) + wave * 1024);
   };
@@ -194,11 +186,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3_bf16_kernel(const bf16_t* __
     issue_halo(c);
 #pragma unroll
     for (int gi = 0; gi < 9; ++gi) {
-      if (DRAM_BF16_ABL == 1 || DRAM_BF16_ABL == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if (DRAM_BF16_ABL == 7) { if (gi == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * WROUNDS) : "memory"); }
-      else if (gi == 0 || (gi == 8 && last)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (gi == 0 || (gi == 8 && last)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WROUNDS) : "memory");
-      if (DRAM_BF16_ABL != 6) __builtin_amdgcn_s_barrier();        // group gi's weights (gi == 0: and the halo) are in LDS for every wave;
+      __builtin_amdgcn_s_barrier();        // group gi's weights (gi == 0: and the halo) are in LDS for every wave;
                                            // slot (gi + 2) % 3, read during group gi - 1, is free
       // (group 0 refills at its END instead: the wait-count pass, which does not see the hand-placed wait, guards
       // the first halo read with its own vmcnt(0) and would wait for a refill issued in front of it)
@@ -213,17 +203,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3_bf16_kernel(const bf16_t* __
       bf16x8 af[2][2], bfr[2][NB];
       auto frag = [&](int st, int buf) __attribute__((always_inline)) {
         const int kx = st >> 1, j = st & 1;
-        if (DRAM_BF16_ABL == 3) {
-#pragma unroll
-          for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) af[buf][mi][e] = (__bf16)(float)(lane + st);
-#pragma unroll
-          for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) bfr[buf][nb][e] = (__bf16)(float)(lane - st);
-          return;
-        }
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
           af[buf][mi] = *reinterpret_cast<const bf16x8*>(halo + abase[mi] + tapo + kx * 64 + (((2 * j + lh) ^ akey[kx]) << 4));
@@ -239,8 +218,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3_bf16_kernel(const bf16_t* __
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
           for (int nb = 0; nb < NB; ++nb)
-            if (DRAM_BF16_ABL == 4) acc[mi][nb][0] += (float)af[st & 1][mi][0] * (float)bfr[st & 1][nb][0];
-            else acc[mi][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[st & 1][mi], bfr[st & 1][nb], acc[mi][nb], 0, 0, 0);
+            acc[mi][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[st & 1][mi], bfr[st & 1][nb], acc[mi][nb], 0, 0, 0);
         if (st + 1 < 6) __builtin_amdgcn_sched_group_barrier(0x100, 2 + NB, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 2 * NB, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -278,7 +256,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv3_bf16_kernel(const bf16_t* __
             v += gate ? (bf16_to_f32(gate[o + nb * 32]) > 0.f ? av : 0.f) : av;
           }
           const bf16_t h = f32_to_bf16(v);
-          if (DRAM_BF16_ABL != 5 || v == 12345.f) y[o + nb * 32] = h;
+          y[o + nb * 32] = h;
           if (EPI == 0) {                  // BatchNorm sums of the values the next pass will read (the rounded ones)
             const float vr = bf16_to_f32(h);
             s1[nb] += vr;
@@ -322,172 +300,6 @@ struct WGeom {
   int nblk;
 };
 
-__global__ __launch_bounds__(512) void wgrad3_bf16_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
-                                                          float* __restrict__ slab, const WGeom g) {
-  __shared__ __attribute__((aligned(1024))) unsigned char halo0[HALO_GRAN * 16];
-  __shared__ __attribute__((aligned(1024))) unsigned char halo1[HALO_GRAN * 16];
-  __shared__ __attribute__((aligned(1024))) unsigned char dyt0[2048 * 16];      // [256 voxels][64 co] bf16
-  __shared__ __attribute__((aligned(1024))) unsigned char dyt1[2048 * 16];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = xcd_remap(blockIdx.x, g.nblk);
-  const int pair = L % g.npairs, split = L / g.npairs;
-  const int cib = pair % g.ci_blocks, cob = pair / g.ci_blocks;
-  const unsigned char* zero = reinterpret_cast<const unsigned char*>(g_zero_page);
-  const CGeom cg{g.B, g.D, g.H, g.W, g.Cin, g.Cout, g.d, g.Tz, g.Ty, g.Tx, 1, 0};
-
-  // Per-lane DMA geometry, fixed for the whole kernel: the halo voxel (hz, hy, hx) / tile voxel (vz, vy, vx) a granule
-  // belongs to and its byte offset relative to the tile's first z plane (32-bit; negative before that plane's first
-  // row is fine: such lanes are out of the volume and never used).  Per tile only the plane base (scalar, in the
-  // buffer descriptor) and the range tests remain -- the first version re-derived everything per tile with 64-bit
-  // arithmetic (~45 VALU instructions per 1-KB piece).
-  int hco[5], hrel[5], vco[4], vrel[4];
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {              // halo: 2560 granules / 512 threads
-    const int p = i * 512 + tid;
-    const int hv = p >> 2, ps = p & 3;
-    const int hz = hv / 100, hy = (hv / 10) % 10, hx = hv % 10;
-    hco[i] = hv < 600 ? (hz << 16) | (hy << 8) | hx : -1;
-    hrel[i] = ((((hz - 1) * g.H + (hy - 1)) * g.W + (hx - 1)) * g.d * g.Cin + cib * 32 + (ps ^ ((hx >> 1) & 3)) * 8) * 2;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {              // dy tile: 256 voxels x 8 slots (64 co); slot ^= 4 * ((v >> 1) & 1)
-    const int q = i * 512 + tid;
-    const int v = q >> 3, ps = q & 7;
-    const int ch = cob * 64 + (ps ^ (((v >> 1) & 1) << 2)) * 8;
-    vco[i] = ch < g.Cout ? ((v >> 6) << 16) | (((v >> 3) & 7) << 8) | (v & 7) : -1;
-    vrel[i] = ((((v >> 6) * g.H + ((v >> 3) & 7)) * g.W + (v & 7)) * g.d * g.Cout + ch) * 2;
-  }
-  const long xbytes = (long)g.B * g.D * g.H * g.W * g.Cin * 2, dbytes = (long)g.B * g.D * g.H * g.W * g.Cout * 2;
-  auto issue_tile = [&](int t, unsigned char* hb, unsigned char* db) __attribute__((always_inline)) {
-    if (DRAM_BF16_ABL == 11) return;
-    int b, rz, ry, rx, lz0, ly0, lx0;
-    decode_tile(t, cg, b, rz, ry, rx, lz0, ly0, lx0);
-    // descriptor bases at the tile's origin voxel (rz + d lz0, ry + d ly0, rx + d lx0): always inside the tensor's
-    // address range for tiles that exist; lanes whose voxel is outside the volume get the out-of-range offset
-    const int oz = rz + g.d * lz0, oy = ry + g.d * ly0, ox = rx + g.d * lx0;
-    const long org = (((long)b * g.D + oz) * g.H + oy) * g.W + ox;
-    // (the halo starts one lattice step BEFORE the origin: offsets are taken from a base moved back by the largest
-    // negative reach, (H W + W + 1) d voxels, clamped into the tensor, and corrected per lane by the same amount)
-    const long back = ((long)g.H * g.W + g.W + 1) * g.d;
-    const long hb0 = org - back < 0 ? 0 : org - back;
-    const int hshift = (int)((org - hb0) * g.Cin * 2);
-    const __amdgpu_buffer_rsrc_t rh = make_rsrc(x, hb0 * g.Cin * 2, xbytes), rd = make_rsrc(dy, org * g.Cout * 2, dbytes);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const int hz = hco[i] >> 16, hy = (hco[i] >> 8) & 255, hx = hco[i] & 255;
-      const int gz = oz + g.d * (hz - 1), gy = oy + g.d * (hy - 1), gx = ox + g.d * (hx - 1);
-      const bool ok = (hco[i] >= 0) & (gz >= 0) & (gz < g.D) & (gy >= 0) & (gy < g.H) & (gx >= 0) & (gx < g.W);
-      BUFLDS16(rh, ok ? (unsigned)(hrel[i] + hshift) : 0xffffffffu, hb + i * 8192 + wave * 1024);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int vz = vco[i] >> 16, vy = (vco[i] >> 8) & 255, vx = vco[i] & 255;
-      const bool ok = (vco[i] >= 0) & (oz + g.d * vz < g.D) & (oy + g.d * vy < g.H) & (ox + g.d * vx < g.W);
-      BUFLDS16(rd, ok ? (unsigned)vrel[i] : 0xffffffffu, db + i * 8192 + wave * 1024);
-    }
-  };
-
-  // this wave: co half cb of the block's 64, taps t0, t0 + 4, ... (7 of them; 6 for t0 == 3)
-  const int cb = wave & 1, t0 = wave >> 1;
-  const int ntap = t0 < 3 ? 7 : 6;
-  f32x16 acc[7];
-#pragma unroll
-  for (int i = 0; i < 7; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-
-  // transposed-read addresses: 16-lane group g4 = lane >> 4 (bit 0: column half, bit 1: k half), lane 4 q + p of a
-  // group addresses row q, the 8-byte piece p of the group's 16 columns
-  const int g4 = lane >> 4, q = (lane >> 2) & 3, p = lane & 3, h = g4 >> 1;
-  const int cslot = (g4 & 1) * 2 + (p >> 1), cbyte = (p & 1) * 8;
-  // A (dy): voxel (zt, 2 yp + h, 4 s + q) of the tile -> byte v * 128 + ((4 cb + cslot) ^ 4 ((v >> 1) & 1)) * 16 + cbyte;
-  // with x = 4 s + q: (v >> 1) & 1 = (q >> 1) & 1 for both s
-  int aoff[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int v = h * 8 + 4 * s + q;
-    aoff[s] = v * 128 + (((4 * cb + cslot) ^ (((v >> 1) & 1) << 2)) << 4) + cbyte;
-  }
-  // B (x halo): voxel (zt + kz, 2 yp + h + ky, 4 s + q + kx) -> byte hv * 64 + (cslot ^ ((hx >> 1) & 3)) * 16 + cbyte
-  int boff[7][2];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    const int tap = (t0 + 4 * i) < 27 ? t0 + 4 * i : 0;
-    const int kz = tap / 9, ky = (tap / 3) % 3, kx = tap % 3;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int hx = 4 * s + q + kx;
-      boff[i][s] = ((kz * 10 + h + ky) * 10 + hx) * 64 + ((cslot ^ ((hx >> 1) & 3)) << 4) + cbyte;
-    }
-  }
-  auto tr8 = [&](const unsigned char* base, int o0, int o1) __attribute__((always_inline)) {
-    const s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + o0));
-    const s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + o1));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7));
-  };
-
-  int t = split;
-  if (t < g.ntile) issue_tile(t, halo0, dyt0);
-  int buf = 0;
-  for (; t < g.ntile; t += g.nsplit, buf ^= 1) {
-    __syncthreads();                                     // tile t has landed; the other buffer pair is free
-    if (t + g.nsplit < g.ntile) {
-      if (buf == 0) issue_tile(t + g.nsplit, halo1, dyt1);
-      else issue_tile(t + g.nsplit, halo0, dyt0);
-    }
-    const unsigned char* hb = buf == 0 ? halo0 : halo1;
-    const unsigned char* db = buf == 0 ? dyt0 : dyt1;
-    // The operand fragments of k16 step ks + 1 (one dy fragment, seven x fragments: 16 transposed reads) are issued
-    // while the seven MFMAs of step ks run.  Left to the compiler every MFMA waited for reads issued ONE MFMA
-    // earlier (32 cycles of cover for >100 cycles of LDS latency): 2.7x the matrix-pipe time per tile.  All seven
-    // accumulators are always fed (a wave with six taps feeds its seventh from tap 0 and never stores it).
-    bf16x8 afr[2], bq[2][7];
-    auto frag = [&](int ks, int bufi) __attribute__((always_inline)) {
-      const int zt = ks >> 2, yp = ks & 3;
-      const unsigned char* da = db + (zt * 64 + yp * 16) * 128;            // voxel (zt, 2 yp, 0)
-      const unsigned char* ha = hb + (zt * 100 + yp * 20) * 64;            // halo voxel (zt, 2 yp, 0)
-      if (DRAM_BF16_ABL == 12) {
-        for (int e = 0; e < 8; ++e) afr[bufi][e] = (__bf16)(float)(lane + ks);
-#pragma unroll
-        for (int i = 0; i < 7; ++i)
-          for (int e = 0; e < 8; ++e) bq[bufi][i][e] = (__bf16)(float)(lane - i);
-        return;
-      }
-      afr[bufi] = tr8(da, aoff[0], aoff[1]);
-#pragma unroll
-      for (int i = 0; i < 7; ++i) bq[bufi][i] = tr8(ha, boff[i][0], boff[i][1]);
-    };
-    frag(0, 0);
-#pragma unroll 2
-    for (int ks = 0; ks < 16; ++ks) {
-      if (ks + 1 < 16) frag(ks + 1, (ks + 1) & 1);
-#pragma unroll
-      for (int i = 0; i < 7; ++i)
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[ks & 1], bq[ks & 1][i], acc[i], 0, 0, 0);
-      if (ks + 1 < 16) __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 7, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-
-  // slab[split][pair][tap][co 64][ci 32]
-  const int li = lane & 31, lh = lane >> 5;
-  float* sb = slab + ((long)split * g.npairs + pair) * 27 * 2048;
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    if (i < ntap) {
-      const int tap = t0 + 4 * i;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = (e & 3) + 8 * (e >> 2) + 4 * lh;
-        sb[(tap * 64 + cb * 32 + row) * 32 + li] = acc[i][e];
-      }
-    }
-  }
-}
-
 __global__ __launch_bounds__(512) void wgrad3b_bf16_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
                                                           float* __restrict__ slab, const WGeom g) {
   __shared__ __attribute__((aligned(1024))) unsigned char halo0[HALO_GRAN * 16];
@@ -527,7 +339,6 @@ __global__ __launch_bounds__(512) void wgrad3b_bf16_kernel(const bf16_t* __restr
   }
   const long xbytes = (long)g.B * g.D * g.H * g.W * g.Cin * 2, dbytes = (long)g.B * g.D * g.H * g.W * g.Cout * 2;
   auto issue_tile = [&](int t, unsigned char* hb, unsigned char* db) __attribute__((always_inline)) {
-    if (DRAM_BF16_ABL == 11) return;
     int b, rz, ry, rx, lz0, ly0, lx0;
     decode_tile(t, cg, b, rz, ry, rx, lz0, ly0, lx0);
     // descriptor bases at the tile's origin voxel (rz + d lz0, ry + d ly0, rx + d lx0): always inside the tensor's
@@ -555,10 +366,10 @@ __global__ __launch_bounds__(512) void wgrad3b_bf16_kernel(const bf16_t* __restr
     }
   };
 
-  // this wave: BOTH co halves of the block's 64, taps wave, wave + 8, wave + 16 (+ 24 for waves 0-2).  The first form
-  // (wgrad3_bf16_kernel: one co half, seven taps per wave) reads 16 operand pieces per 7 MFMAs -- 128 transposed reads
-  // of 512 B per k16 step and workgroup, 512 LDS cycles against 448 matrix cycles: LDS-bound.  Here the dy fragments
-  // serve both halves' accumulators of every tap: 86 reads (344 cycles) per step for the same 54 MFMAs.
+  // this wave: BOTH co halves of the block's 64, taps wave, wave + 8, wave + 16 (+ 24 for waves 0-2).  A first form
+  // (one co half, seven taps per wave) read 16 operand pieces per 7 MFMAs -- 128 transposed reads of 512 B per k16
+  // step and workgroup, 512 LDS cycles against 448 matrix cycles: LDS-bound.  Here the dy fragments serve both
+  // halves' accumulators of every tap: 86 reads (344 cycles) per step for the same 54 MFMAs.
   const int ntap = wave < 3 ? 4 : 3;
   const bool has4 = wave < 3;                    // wave-uniform
   f32x16 acc[4][2];
@@ -606,7 +417,9 @@ __global__ __launch_bounds__(512) void wgrad3b_bf16_kernel(const bf16_t* __restr
   // the DMA issue and the first read of EVERY tile -- the next tile's load was waited for before the current tile's
   // first MFMA (no DMA: -26 % in the ablation was exactly this).  Named objects per phase answer the alias query.
   auto compute = [&](const unsigned char* hb, const unsigned char* db) __attribute__((always_inline)) {
-    // The operand fragments of k16 step ks + 1 are issued while the MFMAs of step ks run (see wgrad3_bf16_kernel).
+    // The operand fragments of k16 step ks + 1 are issued while the MFMAs of step ks run.  Left to the compiler every
+    // MFMA waited for reads issued ONE MFMA earlier (32 cycles of cover for >100 cycles of LDS latency): 2.7x the
+    // matrix-pipe time per tile.
     // The fourth tap of waves 0-2 is a block of its own behind a wave-uniform branch: its reads (next step) and its two
     // MFMAs (this step) are independent of each other.
     bf16x8 afr[2][2], bq[2][4];
@@ -614,13 +427,6 @@ __global__ __launch_bounds__(512) void wgrad3b_bf16_kernel(const bf16_t* __restr
       const int zt = ks >> 2, yp = ks & 3;
       const unsigned char* da = db + (zt * 64 + yp * 16) * 128;            // voxel (zt, 2 yp, 0)
       const unsigned char* ha = hb + (zt * 100 + yp * 20) * 64;            // halo voxel (zt, 2 yp, 0)
-      if (DRAM_BF16_ABL == 12) {           // ablation: no LDS operand reads
-        for (int e = 0; e < 8; ++e) afr[bufi][0][e] = afr[bufi][1][e] = (__bf16)(float)(lane + ks);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-          for (int e = 0; e < 8; ++e) bq[bufi][i][e] = (__bf16)(float)(lane - i);
-        return;
-      }
       afr[bufi][0] = tr8(da, aoff[0][0], aoff[0][1]);
       afr[bufi][1] = tr8(da, aoff[1][0], aoff[1][1]);
 #pragma unroll
@@ -628,31 +434,26 @@ __global__ __launch_bounds__(512) void wgrad3b_bf16_kernel(const bf16_t* __restr
     };
     auto frag4 = [&](int ks, int bufi) __attribute__((always_inline)) {
       const int zt = ks >> 2, yp = ks & 3;
-      if (DRAM_BF16_ABL == 12) { for (int e = 0; e < 8; ++e) bq[bufi][3][e] = (__bf16)(float)(lane - 3); return; }
       bq[bufi][3] = tr8(hb + (zt * 100 + yp * 20) * 64, boff[3][0], boff[3][1]);
     };
     frag(0, 0);
     if (has4) frag4(0, 0);
 #pragma unroll 2
     for (int ks = 0; ks < 16; ++ks) {
-      if (ks + 1 < 16 && DRAM_BF16_ABL != 14) frag(ks + 1, (ks + 1) & 1);     // ablation 14: operands read once per tile
-      if (DRAM_BF16_ABL == 14 && ks == 0) frag(1, 1);
+      if (ks + 1 < 16) frag(ks + 1, (ks + 1) & 1);
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int c = 0; c < 2; ++c)
-          if (DRAM_BF16_ABL == 13) acc[i][c][0] += (float)afr[ks & 1][c][0] * (float)bq[ks & 1][i][0];   // ablation: no MFMAs
-          else acc[i][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[ks & 1][c], bq[ks & 1][i], acc[i][c], 0, 0, 0);
+          acc[i][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[ks & 1][c], bq[ks & 1][i], acc[i][c], 0, 0, 0);
       if (ks + 1 < 16) __builtin_amdgcn_sched_group_barrier(0x100, 10, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
       __builtin_amdgcn_sched_barrier(0);
       if (has4) {
-        if (ks + 1 < 16 && DRAM_BF16_ABL != 14) frag4(ks + 1, (ks + 1) & 1);
-        if (DRAM_BF16_ABL == 14 && ks == 0) frag4(1, 1);
+        if (ks + 1 < 16) frag4(ks + 1, (ks + 1) & 1);
 #pragma unroll
         for (int c = 0; c < 2; ++c)
-          if (DRAM_BF16_ABL == 13) acc[3][c][0] += (float)afr[ks & 1][c][0] * (float)bq[ks & 1][3][0];
-          else acc[3][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[ks & 1][c], bq[ks & 1][3], acc[3][c], 0, 0, 0);
+          acc[3][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[ks & 1][c], bq[ks & 1][3], acc[3][c], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -738,7 +539,7 @@ __global__ __launch_bounds__(512) void wgrad3z_bf16_kernel(const bf16_t* __restr
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][cb][e] = 0.f;
 
-  // transposed-read lane addresses (see wgrad3_bf16_kernel): row q of the group's block, 8-byte piece p
+  // transposed-read lane addresses (see wgrad3b_bf16_kernel): row q of the group's block, 8-byte piece p
   const int g4 = lane >> 4, q = (lane >> 2) & 3, p4 = lane & 3, h = g4 >> 1;
   const int cpiece = ((g4 & 1) * 2 + (p4 >> 1)) * 16 + (p4 & 1) * 8;
   int a_lane[2], b_lane[2];
@@ -1507,7 +1308,7 @@ __global__ void s2_extract_wgrad_kernel(const float* __restrict__ dw3, float* __
   }
 }
 
-inline int ew_grid(long total) { return ew_blocks(total, 256, 8192); }   // one-shot blocks (common.h)
+inline int ew_grid(long total) { return ew_blocks(total, 256); }   // one-shot blocks (common.h)
 
 bool geom1_ok(const DramConvDesc* d) {       // 1x1x1, stride 1: a GEMM over the flat voxel index
   if (!d) return false;
@@ -1602,7 +1403,7 @@ void plan_wgrad(const DramConvDesc* d, WGeom& g) {
   // buffering), at most 256 slabs: a slab is 27 x 2048 floats per (pair, split) and the reduce reads them all
   // (512 -> 512 @ 2x16x32x32, ms: 1024 workgroups 0.69, 512 0.55, 256 0.56; 256 -> 256: 0.40 / 0.26 / 0.19)
   // ... and 576 -> 64 @ 2x32x64x64 (1,024 tiles, 18 pairs): 0.73 / - / 0.93 -- large volumes want the finer split
-  const int wgs = tune_env("DRAM_BF16_WGRAD_WGS") ? atoi(tune_env("DRAM_BF16_WGRAD_WGS")) : (g.ntile >= 512 ? 1024 : 256);
+  const int wgs = g.ntile >= 512 ? 1024 : 256;
   int ns = (wgs + g.npairs - 1) / g.npairs;
   if (ns > g.ntile / 2) ns = g.ntile / 2;
   if (ns > 256) ns = 256;
@@ -1648,8 +1449,7 @@ void plan_zwalk(const DramConvDesc* d, ZGeom& g) {
   const long long cols = (long long)d->B * d->dil * d->dil * d->dil * g.Ty * g.Tx;
   // z segments: enough workgroups for two per CU, never shorter than 4 planes (each segment re-reads 2 halo planes)
   int nzs = 1;
-  static const int zw_wgs = tune_env("DRAM_BF16_ZWALK_WGS") ? atoi(tune_env("DRAM_BF16_ZWALK_WGS")) : 512;     // A/B
-  while (cols * nzs * g.npairs < zw_wgs && g.Lz / (nzs * 2) >= 4) nzs *= 2;
+  while (cols * nzs * g.npairs < 512 && g.Lz / (nzs * 2) >= 4) nzs *= 2;
   g.nzs = nzs;
   g.lseg = (g.Lz + nzs - 1) / nzs;
   g.ncol = (int)(cols * nzs);
@@ -1669,10 +1469,9 @@ int launch_gemm1(const bf16_t* x, const bf16_t* w, const bf16_t* add, const bf16
   g.m_tiles = (int)((g.M + 255) / 256);
   // 128-column tiles, unless they leave the chip under-filled (two workgroups per CU: 512 slots): the 16 x 32 x 32 stages
   // of ResNet-50 have 64 row tiles, so 1024->256 was 128 workgroups on 256 CUs (26 us for 42 MB: 1.6 TB/s).  64-column
-  // tiles double the workgroups; the A tile they re-read comes from L2.  DRAM_BF16_GEMM1_NB=4 (DRAM_TUNING=1): A/B.
+  // tiles double the workgroups; the A tile they re-read comes from L2.
   int nb = cout % 128 == 0 ? 4 : 2;
-  static const int force_nb = tune_env("DRAM_BF16_GEMM1_NB") ? atoi(tune_env("DRAM_BF16_GEMM1_NB")) : 0;
-  if (nb == 4 && force_nb != 4 && (long)g.m_tiles * (cout / 128) < 512) nb = 2;
+  if (nb == 4 && (long)g.m_tiles * (cout / 128) < 512) nb = 2;
   g.n_tiles = cout / (32 * nb);
   g.nblk = g.m_tiles * g.n_tiles;
   DramProf prof(DRAM_FAM_CONV_BF16, 8 + epi * 2 + (nb == 4), 2.0 * (double)g.m_tiles * 256.0 * cin * cout,
@@ -1687,9 +1486,8 @@ int launch_gemm1(const bf16_t* x, const bf16_t* w, const bf16_t* add, const bf16
   return DRAM_OK;
 }
 
-bool wgrad1_big(const DramConvDesc* d) {      // 128 x 128 blocks: from 128 channels on both sides (A/B: DRAM_BF16_WGRAD1=small)
-  static const bool small = tune_env("DRAM_BF16_WGRAD1") && !strcmp(tune_env("DRAM_BF16_WGRAD1"), "small");
-  return !small && d->Cin >= 128 && d->Cout >= 128;
+bool wgrad1_big(const DramConvDesc* d) {      // 128 x 128 blocks: from 128 channels on both sides
+  return d->Cin >= 128 && d->Cout >= 128;
 }
 void plan_wgrad1b(const DramConvDesc* d, W1bGeom& g) {
   g.M = (long)d->B * d->D * d->H * d->W;
@@ -1942,13 +1740,8 @@ extern "C" int dram_conv3d_bwd_weight_bf16(const void* x, const void* dy, float*
   {
     DramProf prof(DRAM_FAM_WGRAD_BF16, 0, 2.0 * (double)g.ntile * 256.0 * 27.0 * g.ci_blocks * 32.0 * g.co_blocks * 64.0,
                   2.0 * vox * (d->Cin + d->Cout) + 4.0 * 27.0 * d->Cin * d->Cout, s, 2.0 * vox * 27.0 * d->Cin * d->Cout);
-    static const bool old_form = tune_env("DRAM_BF16_WGRAD_TILE") && !strcmp(tune_env("DRAM_BF16_WGRAD_TILE"), "old");   // A/B
-    if (old_form)
-      hipLaunchKernelGGL(wgrad3_bf16_kernel, dim3(g.nblk), dim3(512), 0, s, (const bf16_t*)x, (const bf16_t*)dy,
-                         (float*)workspace, g);
-    else
-      hipLaunchKernelGGL(wgrad3b_bf16_kernel, dim3(g.nblk), dim3(512), 0, s, (const bf16_t*)x, (const bf16_t*)dy,
-                         (float*)workspace, g);
+    hipLaunchKernelGGL(wgrad3b_bf16_kernel, dim3(g.nblk), dim3(512), 0, s, (const bf16_t*)x, (const bf16_t*)dy,
+                       (float*)workspace, g);
     DRAM_LAUNCH_CHECK();
   }
   const long n = (long)d->Cout * d->Cin * 27;

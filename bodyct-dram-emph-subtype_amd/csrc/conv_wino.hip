@@ -559,7 +559,7 @@ __constant__ float c_at4[4][6] = {{1, 1, 1, 1, 1, 0}, {0, 1, -1, 2, -2, 0}, {0, 
 // instead of a pass of its own over dz and y.
 struct BnBwdStat { const float* y; const float* mean; const float* invstd; const float* scale; const float* shift; };
 // (F(4,3)^3: four workgroups per CU = 128 registers; the statistics form would otherwise take 129 and lose a wave per SIMD)
-template <int NZ, int NY, int NX, bool NT, int ADD = 0, int BST = 0>
+template <int NZ, int NY, int NX, int ADD = 0, int BST = 0>
 __global__ __launch_bounds__(256, (BST && NZ == 4 && NY == 4 && NX == 4) ? 4 : 1) void wino_out_kernel(const float* __restrict__ mh, const float* __restrict__ bias,
                                                        const float* __restrict__ add, const float* __restrict__ gate,
                                                        float* __restrict__ out, float* __restrict__ stats,
@@ -605,7 +605,7 @@ __global__ __launch_bounds__(256, (BST && NZ == 4 && NY == 4 && NX == 4) ? 4 : 1
 #pragma unroll
           for (int k = 0; k < NK; ++k)
             m[j][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)c4, (int)(sp + (j * NK + k) * pplane),
-                                                                                      NT ? 2 : 0));
+                                                                                      2));
 #pragma unroll
         for (int j = 0; j < NJ; ++j) atz<NX>(m[j], p[j]);
 #pragma unroll
@@ -886,8 +886,7 @@ template <int NJ>
 __global__ __launch_bounds__(512) void wino_gemm_nn_kernel(const float* __restrict__ A, const float* __restrict__ Bw,
                                                            float* __restrict__ Y, const int Mpad, const int N,
                                                            const int K, const int m_tiles, const int n_tiles,
-                                                           const int nblk, const int npts, const GemmEpilogue ep,
-                                                           const int epi_lds) {
+                                                           const int nblk, const int npts, const GemmEpilogue ep) {
   constexpr int BN = 64 * NJ;
   constexpr int STAGE = (256 + BN) * 32;
   __shared__ __attribute__((aligned(1024))) float lds[2 * STAGE];
@@ -981,136 +980,82 @@ __global__ __launch_bounds__(512) void wino_gemm_nn_kernel(const float* __restri
   }
 
   const bool fused = ep.bias || ep.add || ep.stats;       // uniform
-  if (epi_lds) {
-    // Store through LDS (every Winograd-domain GEMM of the pipeline, and the 1x1x1 convolutions with their fused
-    // epilogues): the 32x32 accumulator layout gives a lane ONE column, so direct stores are 32 dword stores per
-    // accumulator in 128-B pieces -- 64 vector-memory instructions per wave behind only 128 MFMAs when K = 64 -- and
-    // the shortcut-gradient epilogue adds two dword loads per element (ResNet-50's 1024->256 data gradient: 186 us
-    // against 81 us for the forward of the same layer).  Each wave turns 32 rows x 64 (32) columns at a time through
-    // a private LDS region (row pitch + 8 floats: the two row groups of a write land in different bank halves) and
-    // moves 16 B per lane: a quarter of the memory instructions, whole 256-B (128-B) row pieces.
-    constexpr int CW = NJ >= 2 ? 64 : 32;                 // columns per round
-    constexpr int NR = NJ >= 2 ? NJ / 2 : 1;              // column rounds
-    constexpr int P = CW + 8;
-    constexpr int Q = CW / 4;                             // 4-column groups per row
-    __syncthreads();                                      // every wave is done with the last operand stage
-    float* reg = lds + wave * (32 * P);
-    const int cq = lane % Q, rs = lane / Q;
-    float s1[NR][4], s2[NR][4];
+  // Store through LDS (every Winograd-domain GEMM of the pipeline, and the 1x1x1 convolutions with their fused
+  // epilogues): the 32x32 accumulator layout gives a lane ONE column, so direct stores are 32 dword stores per
+  // accumulator in 128-B pieces -- 64 vector-memory instructions per wave behind only 128 MFMAs when K = 64 -- and
+  // the shortcut-gradient epilogue adds two dword loads per element (ResNet-50's 1024->256 data gradient: 186 us
+  // against 81 us for the forward of the same layer).  Each wave turns 32 rows x 64 (32) columns at a time through
+  // a private LDS region (row pitch + 8 floats: the two row groups of a write land in different bank halves) and
+  // moves 16 B per lane: a quarter of the memory instructions, whole 256-B (128-B) row pieces.
+  constexpr int CW = NJ >= 2 ? 64 : 32;                 // columns per round
+  constexpr int NR = NJ >= 2 ? NJ / 2 : 1;              // column rounds
+  constexpr int P = CW + 8;
+  constexpr int Q = CW / 4;                             // 4-column groups per row
+  __syncthreads();                                      // every wave is done with the last operand stage
+  float* reg = lds + wave * (32 * P);
+  const int cq = lane % Q, rs = lane / Q;
+  float s1[NR][4], s2[NR][4];
+#pragma unroll
+  for (int cr = 0; cr < NR; ++cr)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { s1[cr][j] = 0.f; s2[cr][j] = 0.f; }
+#pragma unroll
+  for (int cr = 0; cr < NR; ++cr) {
+    const int col = nt * BN + wn * NJ * 32 + cr * CW + 4 * cq;          // column of Y (and of bias)
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (ep.bias) bv = *reinterpret_cast<const f32x4*>(ep.bias + col);
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+#pragma unroll
+        for (int j = 0; j < CW / 32; ++j)
+          reg[((e & 3) + 8 * (e >> 2) + 4 * lh) * P + j * 32 + li] = acc[mi][cr * (CW / 32) + j][e];
+#pragma unroll
+      for (int r = 0; r < 32 / (64 / Q); ++r) {
+        const int row = r * (64 / Q) + rs;
+        f32x4 v = *reinterpret_cast<const f32x4*>(reg + row * P + 4 * cq);
+        float* o = Yb + (long)(wm * 64 + mi * 32 + row) * N + wn * NJ * 32 + cr * CW + 4 * cq;
+        if (fused) {
+          v += bv;
+          if (ep.add) {
+            const long oo = o - Y;
+            const f32x4 av = *reinterpret_cast<const f32x4*>(ep.add + oo);
+            if (ep.gate) {
+              const f32x4 gv = *reinterpret_cast<const f32x4*>(ep.gate + oo);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) v[j] += gv[j] > 0.f ? av[j] : 0.f;
+            } else {
+              v += av;
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { s1[cr][j] += v[j]; s2[cr][j] += v[j] * v[j]; }
+        }
+        *reinterpret_cast<f32x4*>(o) = v;
+      }
+    }
+  }
+  if (ep.stats) {
 #pragma unroll
     for (int cr = 0; cr < NR; ++cr)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { s1[cr][j] = 0.f; s2[cr][j] = 0.f; }
+      for (int j = 0; j < 4; ++j)
 #pragma unroll
-    for (int cr = 0; cr < NR; ++cr) {
-      const int col = nt * BN + wn * NJ * 32 + cr * CW + 4 * cq;          // column of Y (and of bias)
-      f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-      if (ep.bias) bv = *reinterpret_cast<const f32x4*>(ep.bias + col);
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-#pragma unroll
-          for (int j = 0; j < CW / 32; ++j)
-            reg[((e & 3) + 8 * (e >> 2) + 4 * lh) * P + j * 32 + li] = acc[mi][cr * (CW / 32) + j][e];
-#pragma unroll
-        for (int r = 0; r < 32 / (64 / Q); ++r) {
-          const int row = r * (64 / Q) + rs;
-          f32x4 v = *reinterpret_cast<const f32x4*>(reg + row * P + 4 * cq);
-          float* o = Yb + (long)(wm * 64 + mi * 32 + row) * N + wn * NJ * 32 + cr * CW + 4 * cq;
-          if (fused) {
-            v += bv;
-            if (ep.add) {
-              const long oo = o - Y;
-              const f32x4 av = *reinterpret_cast<const f32x4*>(ep.add + oo);
-              if (ep.gate) {
-                const f32x4 gv = *reinterpret_cast<const f32x4*>(ep.gate + oo);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] += gv[j] > 0.f ? av[j] : 0.f;
-              } else {
-                v += av;
-              }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { s1[cr][j] += v[j]; s2[cr][j] += v[j] * v[j]; }
-          }
-          *reinterpret_cast<f32x4*>(o) = v;
+        for (int o = Q; o < 64; o <<= 1) {
+          s1[cr][j] += __shfl_xor(s1[cr][j], o, 64);
+          s2[cr][j] += __shfl_xor(s2[cr][j], o, 64);
         }
-      }
-    }
-    if (ep.stats) {
+    __syncthreads();                                    // every wave is done with its turn region
+    float* red = lds;  // [8 waves][2][32 * NJ]
+    if (rs == 0) {
 #pragma unroll
       for (int cr = 0; cr < NR; ++cr)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int o = Q; o < 64; o <<= 1) {
-            s1[cr][j] += __shfl_xor(s1[cr][j], o, 64);
-            s2[cr][j] += __shfl_xor(s2[cr][j], o, 64);
-          }
-      __syncthreads();                                    // every wave is done with its turn region
-      float* red = lds;  // [8 waves][2][32 * NJ]
-      if (rs == 0) {
-#pragma unroll
-        for (int cr = 0; cr < NR; ++cr)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            red[(wave * 2 + 0) * 32 * NJ + cr * CW + 4 * cq + j] = s1[cr][j];
-            red[(wave * 2 + 1) * 32 * NJ + cr * CW + 4 * cq + j] = s2[cr][j];
-          }
-      }
-      __syncthreads();
-      if (tid < 2 * BN) {
-        const int which = tid / BN, cc = tid - which * BN;       // column within the workgroup's BN
-        const int cwn = cc / (32 * NJ), c2 = cc - cwn * 32 * NJ;
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) v += red[((cwn * 4 + w) * 2 + which) * 32 * NJ + c2];   // wave = wn * 4 + wm
-        ep.stats[((long)mt * 2 + which) * N + nt * BN + cc] = v;
-      }
-    }
-    return;
-  }
-  float s1[NJ], s2[NJ], bv[NJ];
-#pragma unroll
-  for (int nj = 0; nj < NJ; ++nj) {
-    s1[nj] = 0.f;
-    s2[nj] = 0.f;
-    bv[nj] = ep.bias ? ep.bias[nt * BN + wn * NJ * 32 + nj * 32 + li] : 0.f;
-  }
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int row = wm * 64 + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-      float* o = Yb + (long)row * N + wn * NJ * 32 + li;
-#pragma unroll
-      for (int nj = 0; nj < NJ; ++nj) {
-        float v = acc[mi][nj][e];
-        if (fused) {
-          v += bv[nj];
-          if (ep.add) {
-            const long oo = (o + nj * 32) - Y;
-            const float av = ep.add[oo];
-            v += ep.gate ? (ep.gate[oo] > 0.f ? av : 0.f) : av;
-          }
-          s1[nj] += v;
-          s2[nj] += v * v;
+        for (int j = 0; j < 4; ++j) {
+          red[(wave * 2 + 0) * 32 * NJ + cr * CW + 4 * cq + j] = s1[cr][j];
+          red[(wave * 2 + 1) * 32 * NJ + cr * CW + 4 * cq + j] = s2[cr][j];
         }
-        o[nj * 32] = v;
-      }
-    }
-  if (ep.stats) {
-    __syncthreads();
-    float* red = lds;  // [8 waves][2][32 * NJ]
-#pragma unroll
-    for (int nj = 0; nj < NJ; ++nj) {
-      const float t1 = s1[nj] + __shfl_xor(s1[nj], 32, 64);
-      const float t2 = s2[nj] + __shfl_xor(s2[nj], 32, 64);
-      if (lh == 0) {
-        red[(wave * 2 + 0) * 32 * NJ + nj * 32 + li] = t1;
-        red[(wave * 2 + 1) * 32 * NJ + nj * 32 + li] = t2;
-      }
     }
     __syncthreads();
     if (tid < 2 * BN) {
@@ -2121,19 +2066,14 @@ bool plan_tn(const DramConvDesc* d, const WinoGeom& g, TnPlan& p) {
   return true;
 }
 
-// streaming (non-temporal) cache policy on the Winograd-domain images, which are written once and read once:
-// bit 0 the input transform's stores, bit 1 the output transform's loads   (DRAM_WINO_NT, A/B switch)
-int wino_nt() {
-  static const int v = tune_env("DRAM_WINO_NT") ? atoi(tune_env("DRAM_WINO_NT")) : 3;
-  return v;
-}
-
 int grid_for(long waves) {
   long b = (waves + 3) / 4;
   return (int)(b > 65536 ? 65536 : (b < 1 ? 1 : b));
 }
 
-// tile transform into the Winograd domain (MODE 0: B^T x B, MODE 1: A dy A^T), fp32 or split-bf16 image
+// tile transform into the Winograd domain (MODE 0: B^T x B, MODE 1: A dy A^T), fp32 or split-bf16 image.  The fp32
+// F(4,3)^3 images are written once and read once: streaming (non-temporal) cache policy on the input transform's
+// stores and the output transform's loads.
 template <int MODE>
 int launch_wino_in(const float* src, float* dst, const WinoGeom& g, const int C, const int math, hipStream_t s,
                    const float* pscale = nullptr, const float* pshift = nullptr, const int Cd = 0, const int cofs = 0) {
@@ -2145,8 +2085,7 @@ int launch_wino_in(const float* src, float* dst, const WinoGeom& g, const int C,
     const double in_elems = (double)g.B * g.D * g.H * g.W * C;
     DramProf prof(DRAM_FAM_WINO_IN, 9444, 0.0, 4.0 * (in_elems + (double)g.npts * g.Tpad * C), s);
     if constexpr (MODE == 0) {
-      if (wino_nt() & 1) hipLaunchKernelGGL((wino_in444_kernel<0, false, true, true>), dim3(grid_for(2 * units)), dim3(256), 0, s, src, dst, g, C, pscale, pshift, Cd, cofs);
-      else hipLaunchKernelGGL((wino_in444_kernel<0, false, false, true>), dim3(grid_for(2 * units)), dim3(256), 0, s, src, dst, g, C, pscale, pshift, Cd, cofs);
+      hipLaunchKernelGGL((wino_in444_kernel<0, false, true, true>), dim3(grid_for(2 * units)), dim3(256), 0, s, src, dst, g, C, pscale, pshift, Cd, cofs);
     }
     DRAM_LAUNCH_CHECK();
     return DRAM_OK;
@@ -2155,11 +2094,9 @@ int launch_wino_in(const float* src, float* dst, const WinoGeom& g, const int C,
   const double in_elems = (double)g.B * g.D * g.H * g.W * C;
   DramProf prof(DRAM_FAM_WINO_IN, MODE * 1000 + g.nz * 100 + g.ny * 10 + g.nx, 0.0,
                 4.0 * (in_elems + (double)g.npts * g.Tpad * C), s);
-  static const int half = tune_env("DRAM_WINO_HALF") ? atoi(tune_env("DRAM_WINO_HALF")) : 1;   // A/B switch (tools)
-  if ((half || Cd) && g.nz == 4 && g.ny == 4 && g.nx == 4) {
+  if (g.nz == 4 && g.ny == 4 && g.nx == 4) {     // two half-tile units per tile (wino_in444_kernel)
     if (math) hipLaunchKernelGGL((wino_in444_kernel<MODE, true, false>), dim3(grid_for(2 * units)), dim3(256), 0, s, src, dst, g, C, nullptr, nullptr, 0, 0);
-    else if (wino_nt() & 1) hipLaunchKernelGGL((wino_in444_kernel<MODE, false, true>), dim3(grid_for(2 * units)), dim3(256), 0, s, src, dst, g, C, nullptr, nullptr, Cd, cofs);
-    else hipLaunchKernelGGL((wino_in444_kernel<MODE, false, false>), dim3(grid_for(2 * units)), dim3(256), 0, s, src, dst, g, C, nullptr, nullptr, Cd, cofs);
+    else hipLaunchKernelGGL((wino_in444_kernel<MODE, false, true>), dim3(grid_for(2 * units)), dim3(256), 0, s, src, dst, g, C, nullptr, nullptr, Cd, cofs);
     DRAM_LAUNCH_CHECK();
     return DRAM_OK;
   }
@@ -2170,7 +2107,9 @@ int launch_wino_in(const float* src, float* dst, const WinoGeom& g, const int C,
     else                                                                                                           \
       hipLaunchKernelGGL((wino_in_kernel<MODE, NZ_, NY_, NX_, false>), dim3(grid_for(units)), dim3(256), 0, s, src, dst, g, C); \
   } while (0)
-  WINO_TILING_DISPATCH(g, W_IN1);
+  if (g.nz == 4 && g.ny == 4) W_IN1(4, 4, 2);
+  else if (g.nz == 4) W_IN1(4, 2, 2);
+  else W_IN1(2, 2, 2);
 #undef W_IN1
   DRAM_LAUNCH_CHECK();
   return DRAM_OK;
@@ -2192,7 +2131,6 @@ int run_nn(const float* A, const float* U, float* Y, const WinoGeom& g, int N, i
     const double cost = (double)((wgs + 255) / 256) * c * (c == 4 ? 1.0 : (c == 2 ? 1.03 : 1.10));
     if (cost < best) { best = cost; nj = c; }
   }
-  if (const char* e = tune_env("DRAM_NN_NJ")) { const int v = atoi(e); if ((v == 1 || v == 2 || v == 4) && N % (64 * v) == 0) nj = v; }
   const int n_tiles = N / (64 * nj);
   const int nblk = g.npts * m_tiles * n_tiles;
   // executed: 2*M*N*K per point; algorithmic bytes: A, U read once, Y written once
@@ -2211,8 +2149,7 @@ int run_nn(const float* A, const float* U, float* Y, const WinoGeom& g, int N, i
   }
 #define WNN(NJ_)                                                                                                   \
   hipLaunchKernelGGL((wino_gemm_nn_kernel<NJ_>), dim3(nblk), dim3(512), 0, s, A, U, Y, g.Tpad, N, K, m_tiles, n_tiles, \
-                     nblk, g.npts, ep, epi_lds)
-  static const int epi_lds = tune_env("DRAM_WINO_EPI") ? atoi(tune_env("DRAM_WINO_EPI")) : 1;      // A/B switch
+                     nblk, g.npts, ep)
   // HBM-bound shapes of the pipeline (no epilogue, whole K in one stage): the persistent streaming form
   const char* se = tune_env("DRAM_NN_STREAM");           // 0 off, 1 from 4 096 items on (default), 2 always (tests)
   const int stream_on = se ? atoi(se) : 1;
@@ -2248,7 +2185,7 @@ int run_nn(const float* A, const float* U, float* Y, const WinoGeom& g, int N, i
         } else WNS(1, 128, 3);
       }
       else if (N == 64 && K == 128) WNS(1, 128, 3);
-      else if (N == 64 && sdb)
+      else if (N == 64 && (sdb & 1))
         hipLaunchKernelGGL((wino_gemm_nn_stream_kernel<1, 64, 3, true>), dim3(grid2), dim3(256), 0, s, A, U, Y, g.npts, m64,
                            per2, (int)total);
       else if (N == 128 && (sdb & 2))
@@ -2268,7 +2205,7 @@ int run_nn(const float* A, const float* U, float* Y, const WinoGeom& g, int N, i
   // (256-column tiles: accumulators + state spill.  Fused epilogues -- the 1x1x1 convolutions of the Bottleneck blocks --
   // keep the one-tile kernel: their bias / shortcut-gradient loads wait on vmcnt, which the prefetch DMA shares, so the
   // epilogue serialises behind the prefetch it was meant to hide: ResNet-50 fp32 38.8 -> 45.6 ms with it, measured)
-  if (persist && epi_lds && !fused && nj <= 2 && (K / 32) % 2 == 0) {
+  if (persist && !fused && nj <= 2 && (K / 32) % 2 == 0) {
     // every workgroup the same number of tiles where that costs no round: 432 tiles -> 216 workgroups x 2 (the other
     // 40 CUs stay free for the second stream's kernels) instead of 176 x 2 + 80 x 1
     const int rounds = (nblk + 255) / 256;
@@ -2320,29 +2257,23 @@ int run_conv(const float* in, const float* U, const float* bias, const float* ad
   const double out_elems = (double)g.B * g.D * g.H * g.W * N;
   DramProf prof(DRAM_FAM_WINO_OUT, g.nz * 100 + g.ny * 10 + g.nx, 0.0,
                 4.0 * ((double)g.npts * g.Tpad * N + out_elems * (1 + (add ? 1 : 0) + (gate ? 1 : 0) + (bst.y ? 1 : 0))), s);
-#define W_OUT2(NZ_, NY_, NX_, NT_)                                                                                        \
-  do {                                                                                                                    \
-    if (add && gate)                                                                                                      \
-      hipLaunchKernelGGL((wino_out_kernel<NZ_, NY_, NX_, NT_, 2>), dim3(ntb * (N / 64)), dim3(256), 0, s, Mh, bias, add,     \
-                         gate, out, stats, g, N, bst);                                                                    \
-    else if (add)                                                                                                         \
-      hipLaunchKernelGGL((wino_out_kernel<NZ_, NY_, NX_, NT_, 1>), dim3(ntb * (N / 64)), dim3(256), 0, s, Mh, bias, add,     \
-                         gate, out, stats, g, N, bst);                                                                    \
-    else if (bst.y)                                                                                                       \
-      hipLaunchKernelGGL((wino_out_kernel<NZ_, NY_, NX_, NT_, 0, 1>), dim3(ntb * (N / 64)), dim3(256), 0, s, Mh, bias, add,  \
-                         gate, out, stats, g, N, bst);                                                                    \
-    else                                                                                                                  \
-      hipLaunchKernelGGL((wino_out_kernel<NZ_, NY_, NX_, NT_, 0>), dim3(ntb * (N / 64)), dim3(256), 0, s, Mh, bias, add,     \
-                         gate, out, stats, g, N, bst);                                                                    \
-  } while (0)
 #define W_OUT(NZ_, NY_, NX_)                                                                                              \
   do {                                                                                                                    \
-    if (wino_nt() & 2) W_OUT2(NZ_, NY_, NX_, true);                                                                       \
-    else W_OUT2(NZ_, NY_, NX_, false);                                                                                    \
+    if (add && gate)                                                                                                      \
+      hipLaunchKernelGGL((wino_out_kernel<NZ_, NY_, NX_, 2>), dim3(ntb * (N / 64)), dim3(256), 0, s, Mh, bias, add,          \
+                         gate, out, stats, g, N, bst);                                                                    \
+    else if (add)                                                                                                         \
+      hipLaunchKernelGGL((wino_out_kernel<NZ_, NY_, NX_, 1>), dim3(ntb * (N / 64)), dim3(256), 0, s, Mh, bias, add,          \
+                         gate, out, stats, g, N, bst);                                                                    \
+    else if (bst.y)                                                                                                       \
+      hipLaunchKernelGGL((wino_out_kernel<NZ_, NY_, NX_, 0, 1>), dim3(ntb * (N / 64)), dim3(256), 0, s, Mh, bias, add,       \
+                         gate, out, stats, g, N, bst);                                                                    \
+    else                                                                                                                  \
+      hipLaunchKernelGGL((wino_out_kernel<NZ_, NY_, NX_, 0>), dim3(ntb * (N / 64)), dim3(256), 0, s, Mh, bias, add,          \
+                         gate, out, stats, g, N, bst);                                                                    \
   } while (0)
   WINO_TILING_DISPATCH(g, W_OUT);
 #undef W_OUT
-#undef W_OUT2
   DRAM_LAUNCH_CHECK();
   return DRAM_OK;
 }
@@ -2545,13 +2476,12 @@ extern "C" int dram_conv_algo(const DramConvDesc* d) {
     // hands its transformed input to the weight gradient (1.59 against 1.83 ms).  The cheaper estimate now wins on the
     // LAST decoder stage (D >= 64: its rounding reaches the output un-amplified), not below it: with layer1 / us1 of
     // ResNet-50 on the pipeline the full-size dRAM volumes sit 1.47e-3 from the fp64 oracle (bar 1e-3; 54 BatchNorm
-    // layers amplify an early error), with the margin kept there they pass as before.  (DRAM_W2D_MARGIN[_BIG]: A/B)
-    const char* me = tune_env(d->D >= 64 ? "DRAM_W2D_MARGIN_BIG" : "DRAM_W2D_MARGIN");
+    // layers amplify an early error), with the margin kept there they pass as before.
     // Round 5: the caller may say that its network amplifies a layer's rounding little (DRAM_CONV_ROUNDING_TOLERANT: the
     // BasicBlock ResNets -- full-size outputs 6.0e-5 / 1.9e-4 from the fp64 oracle with every 64->64 layer on F(4,3)^3):
     // the cheaper estimate then wins everywhere (config 1: 39.6 -> 38.5 ms).
     const bool tolerant = (d->flags & DRAM_CONV_ROUNDING_TOLERANT) != 0;
-    const double margin = me ? atof(me) : ((d->D >= 64 || tolerant) ? 1.0 : 1.15);
+    const double margin = (d->D >= 64 || tolerant) ? 1.0 : 1.15;
     if (w2d < 0.92 * direct && w2d < margin * best) { best = w2d; pick = 2; }
   }
   return pick;
@@ -2600,9 +2530,7 @@ extern "C" int dram_conv_wgrad_algo(const DramConvDesc* d) {
     // including the transform of x that the fused forward kernel did not leave behind.  64->64 @ 2x32x64x64: kernel
     // times are level (0.24 vs 0.26 ms), but on the second stream the pipeline's HBM-bound transforms overlap the
     // matrix-bound data-gradient chain where the z-walking kernel competes with it: config 1 40.95 -> 40.14 ms.
-    const char* mw = tune_env("DRAM_WGRAD_MARGIN");                        // A/B
-    const double margin = mw ? atof(mw) : 1.0;
-    if (w2d < 0.92 * direct && w2d < margin * best) { best = w2d; pick = 2; }
+    if (w2d < 0.92 * direct && w2d < best) { best = w2d; pick = 2; }
   }
   return pick;
 }
@@ -2766,8 +2694,7 @@ extern "C" int dram_wino_conv3d_bwd_weight(const float* x, const float* v_cache,
       hipLaunchKernelGGL((wino_gemm_tn_kernel<WM_, MI_, NJ_>), dim3(nblk), dim3(512), 0, s, Dh, V, slab, g.Tpad,       \
                          d->Cout, d->Cin, p.m_tiles, p.n_tiles, p.nsplit, p.kper, nblk, g.npts);                       \
   } while (0)
-  static const int tn64 = tune_env("DRAM_TN64") ? atoi(tune_env("DRAM_TN64")) : 1;      // A/B switch
-  if (tn64 && math == 0 && d->Cout == 64 && d->Cin == 64 && p.kper % 64 == 0 && g.Tpad % 64 == 0)
+  if (math == 0 && d->Cout == 64 && d->Cin == 64 && p.kper % 64 == 0 && g.Tpad % 64 == 0)
     hipLaunchKernelGGL(wino_gemm_tn64_kernel, dim3(g.npts * p.nsplit), dim3(512), 0, s, Dh, V, slab, g.Tpad, p.nsplit,
                        p.kper, g.npts * p.nsplit, g.npts);
   else if (p.bm == 256 && p.bn == 256) WTN(4, 2, 4);

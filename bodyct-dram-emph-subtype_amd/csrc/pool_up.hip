@@ -4,14 +4,13 @@
 // align_corners=True) + crop_concat_5d (med3d.py:83-87, :39-48), F.interpolate at
 // models.py:438-441, and their autograd backward.  HBM-bound; float4 = 4 channels/lane.
 #include <stdlib.h>
-#include <string.h>
 #include <initializer_list>
 #include "common.h"
 
 namespace {
 
 // one-shot blocks (common.h, ew_blocks): each loop below then runs once per thread
-inline int ew_grid(long total) { return ew_blocks(total, 256, 8192); }
+inline int ew_grid(long total) { return ew_blocks(total, 256); }
 
 // ------------------------------------------------------------------ max pool
 // A thread owns VW channels of one voxel (VW * sizeof(T) = 16 B where the channel count allows: common.h, fvec).
@@ -141,74 +140,11 @@ __global__ void bn_maxpool_fwd_kernel(const T* __restrict__ yin, const float* __
   }
 }
 
-template <typename T, int VW>
-__global__ void maxpool_bwd_kernel(const T* __restrict__ dy, const uint8_t* __restrict__ amax,
-                                   const T* __restrict__ add, int add_stride, T* __restrict__ dx, int D, int H,
-                                   int W, int C, int Do, int Ho, int Wo, long total) {
-  const int Q = C / VW;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int q = (int)(i % Q);
-    long v = i / Q;
-    const int xi = (int)(v % W); v /= W;
-    const int yi = (int)(v % H); v /= H;
-    const int zi = (int)(v % D);
-    const long b = v / D;
-    // add: a tensor shaped like dx, or a channel slice of a wider one (add_stride elements per voxel)
-    fvec<VW> s;
-    if (add) s = ldv<T, VW>(add, (i / Q) * (long)add_stride + VW * q);
-    else {
-#pragma unroll
-      for (int k = 0; k < VW; ++k) s.v[k] = 0.f;
-    }
-    // windows containing zi: zo with 2zo-1 <= zi <= 2zo+1
-    const int zlo = zi >> 1, zhi = (zi + 1) >> 1;  // ceil((zi-1)/2) == zi>>1 for zi>=0
-    const int ylo = yi >> 1, yhi = (yi + 1) >> 1;
-    const int xlo = xi >> 1, xhi = (xi + 1) >> 1;
-    // the (up to) 2 x 2 x 2 windows containing this voxel: all eight (argmax, dy) pairs are loaded together with
-    // clamped window indices, invalid ones are skipped afterwards -- in the original scan order
-    uchar4 am[2][2][2][VW / 4];
-    fvec<VW> gg[2][2][2];
-#pragma unroll
-    for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-      for (int dy_ = 0; dy_ < 2; ++dy_)
-#pragma unroll
-        for (int dx_ = 0; dx_ < 2; ++dx_) {
-          const int zo = min(zlo + dz, Do - 1), yo = min(ylo + dy_, Ho - 1), xo = min(xlo + dx_, Wo - 1);
-          const long o = ((((b * Do + zo) * Ho + yo) * Wo + xo) * (long)Q + q);
-#pragma unroll
-          for (int k = 0; k < VW / 4; ++k) am[dz][dy_][dx_][k] = reinterpret_cast<const uchar4*>(amax)[(VW / 4) * o + k];
-          gg[dz][dy_][dx_] = ldv<T, VW>(dy, VW * o);
-        }
-#pragma unroll
-    for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-      for (int dy_ = 0; dy_ < 2; ++dy_)
-#pragma unroll
-        for (int dx_ = 0; dx_ < 2; ++dx_) {
-          const int zo = zlo + dz, yo = ylo + dy_, xo = xlo + dx_;
-          if (zo > zhi || zo >= Do || yo > yhi || yo >= Ho || xo > xhi || xo >= Wo) continue;
-          const int kz = zi - (2 * zo - 1), ky = yi - (2 * yo - 1), kx = xi - (2 * xo - 1);
-          const unsigned char tap = (unsigned char)((kz * 3 + ky) * 3 + kx);
-#pragma unroll
-          for (int k = 0; k < VW / 4; ++k) {
-            const uchar4 a = am[dz][dy_][dx_][k];
-            const fvec<VW>& g = gg[dz][dy_][dx_];
-            if (a.x == tap) s.v[4 * k] += g.v[4 * k];
-            if (a.y == tap) s.v[4 * k + 1] += g.v[4 * k + 1];
-            if (a.z == tap) s.v[4 * k + 2] += g.v[4 * k + 2];
-            if (a.w == tap) s.v[4 * k + 3] += g.v[4 * k + 3];
-          }
-        }
-    stv<T, VW>(dx, VW * i, s);
-  }
-}
-
-// The same gradient with one thread per 2 x 2 x 2 block of input voxels: the block's voxels lie in the (up to) eight
+// Max-pool gradient with one thread per 2 x 2 x 2 block of input voxels: the block's voxels lie in the (up to) eight
 // windows {a, a + 1}^3 only -- per axis an even coordinate 2a belongs to window a (tap 1), an odd one 2a + 1 to
 // windows a (tap 2) and a + 1 (tap 0) -- so the eight (argmax, dy) pairs are loaded ONCE per block instead of once
-// per voxel (16 + 8 loads per 8 voxels instead of 136; the per-voxel kernel ran at 2.9 TB/s on its gathers).
-// Contributions are added in the per-voxel kernel's window order: bit-identical results.
+// per voxel (16 + 8 loads per 8 voxels instead of 136; a kernel with one thread per voxel ran at 2.9 TB/s on its
+// gathers).  A voxel's contributions are added in ascending window order (z, y, x).
 template <typename T, int VW>
 __global__ void maxpool_bwd_blk_kernel(const T* __restrict__ dy, const uint8_t* __restrict__ amax,
                                        const T* __restrict__ add, int add_stride, T* __restrict__ dx, int D, int H,
@@ -542,10 +478,9 @@ inline float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (flo
 }  // namespace
 
 // channels per thread: 8 for bf16 storage when every channel count / stride involved is a multiple of 8 (16-B
-// vectors), else 4.  DRAM_POOL_VW=4 forces the narrow form (A/B).
+// vectors), else 4.
 static inline bool pool_wide(size_t elem, std::initializer_list<long> counts) {
-  static const bool narrow = tune_env("DRAM_POOL_VW") && atoi(tune_env("DRAM_POOL_VW")) == 4;
-  if (elem != 2 || narrow) return false;
+  if (elem != 2) return false;
   for (long c : counts)
     if (c & 7) return false;
   return true;
@@ -618,15 +553,8 @@ static int maxpool_bwd_impl(const T* dy, const uint8_t* argmax, const T* add, in
                 (double)sizeof(T) * 4.0 * total4 * (1.0 + (add ? 1 : 0)) + (1.0 + sizeof(T)) * (double)B * Do * Ho * Wo * C,
                 (hipStream_t)stream);
   const bool wide = pool_wide(sizeof(T), {C, add ? add_stride : 0, (add && ((uintptr_t)add & 15)) ? 1 : 0});
-  static const bool per_voxel = tune_env("DRAM_POOL_BWD") && !strcmp(tune_env("DRAM_POOL_BWD"), "voxel");     // A/B
-  if (!per_voxel) {
-    const long totb = (long)B * ((D + 1) / 2) * ((H + 1) / 2) * ((W + 1) / 2) * (C / (wide ? 8 : 4));
-    POOL_LAUNCH(wide, maxpool_bwd_blk_kernel, ew_grid(totb), dy, argmax, add, add_stride, dx, D, H, W, C, Do, Ho, Wo, totb);
-    DRAM_LAUNCH_CHECK();
-    return DRAM_OK;
-  }
-  const long total = wide ? total4 / 2 : total4;
-  POOL_LAUNCH(wide, maxpool_bwd_kernel, ew_grid(total), dy, argmax, add, add_stride, dx, D, H, W, C, Do, Ho, Wo, total);
+  const long totb = (long)B * ((D + 1) / 2) * ((H + 1) / 2) * ((W + 1) / 2) * (C / (wide ? 8 : 4));
+  POOL_LAUNCH(wide, maxpool_bwd_blk_kernel, ew_grid(totb), dy, argmax, add, add_stride, dx, D, H, W, C, Do, Ho, Wo, totb);
   DRAM_LAUNCH_CHECK();
   return DRAM_OK;
 }

@@ -438,6 +438,55 @@ def test_streaming_kernels_carry_no_hidden_lds_or_spills():
         assert vgpr <= 128, l
 
 
+# the tuning switches of DESIGN.md, "Tuning switches": what the library reads through tune_env (csrc/common.h) ...
+TUNE_ENV_CPP = {
+    "DRAM_CONV_ALGO", "DRAM_WINO_TILING", "DRAM_MATH", "DRAM_W2D_V", "DRAM_IGEMM_V", "DRAM_IGEMM_V3_FORCE", "DRAM_WGRAD_V",
+    "DRAM_NN_STREAM", "DRAM_NN_STREAM_DB", "DRAM_NN_PERSIST", "DRAM_UPCAT_UNTILED", "DRAM_BF16_NW", "DRAM_BF16_WGRAD",
+}
+# ... and what the package reads through ops.tuning_env
+TUNE_ENV_PY = {
+    "DRAM_UPMIX", "DRAM_BF16_S2", "DRAM_STEM_BF16", "DRAM_BWD_BNSTATS", "DRAM_BN_PROLOGUE", "DRAM_CONV_CAT",
+    "DRAM_WGRAD_STREAM", "DRAM_SIDE_PRIORITY", "DRAM_INFLIGHT", "DRAM_GRAPH_STREAMS", "DRAM_DIST_TRANSPORT",
+}
+# settled A/B switches, retired with the kernel forms only they reached (suffixes: this file must not name them either)
+RETIRED_SUFFIXES = ("WINO_NT", "WINO_HALF", "NN_NJ", "WINO_EPI", "TN64", "W2D_MARGIN", "W2D_MARGIN_BIG", "WGRAD_MARGIN",
+                    "BF16_WGRAD_WGS", "BF16_ZWALK_WGS", "BF16_GEMM1_NB", "BF16_WGRAD1", "BF16_WGRAD_TILE", "BF16_ABL",
+                    "POOL_VW", "POOL_BWD", "EW_SHAPE", "EW_U")
+
+
+def test_tuning_switches_are_the_documented_set():
+    """Every switch the library reads through tune_env() and the package through tuning_env() has a row in DESIGN.md's
+    table (mirrored above): a new switch needs a row there, and a key in ops._PLAN_ENV if a plan function reads it.  The
+    retired A/B switches are named nowhere in the sources, the tools or the tests."""
+    import glob
+    from bodyct_dram_emph_subtype_amd import ops
+    pkg = os.path.join(ROOT, "bodyct-dram-emph-subtype_amd")
+
+    def literals(files, call):
+        found = set()
+        for f in files:
+            found |= set(re.findall(call + r"""\(\s*["'](DRAM_[A-Z0-9_]+)["']""", open(f).read()))
+        return found
+
+    csrc = glob.glob(os.path.join(pkg, "csrc", "*"))
+    assert literals(csrc, "tune_env") == TUNE_ENV_CPP
+    # (every tune_env argument is a literal the scan above can see: no computed names)
+    calls = sum(len(re.findall(r"\btune_env\(", open(f).read())) for f in csrc)
+    assert calls == sum(len(re.findall(r"""\btune_env\(\s*["']DRAM_""", open(f).read())) for f in csrc) + 1    # + the definition
+    assert literals(glob.glob(os.path.join(pkg, "*.py")), "tuning_env") == TUNE_ENV_PY
+    assert set(ops._PLAN_ENV) <= TUNE_ENV_CPP
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    for name in TUNE_ENV_CPP | TUNE_ENV_PY:
+        assert "| `%s` |" % name in design, name
+    retired = re.compile(r"\bDRAM_(%s)\b" % "|".join(RETIRED_SUFFIXES))
+    files = csrc + glob.glob(os.path.join(pkg, "*.py"))
+    for sub in ("tools", "tests"):
+        files += [f for f in glob.glob(os.path.join(ROOT, sub, "*")) if os.path.isfile(f)]
+    for f in files:
+        m = retired.search(open(f, errors="replace").read())
+        assert m is None, (f, m.group(0))
+
+
 def test_rccl_c_api_binding_loads_every_symbol_it_calls():
     """rccl.py binds librccl's C API by ctypes (the data-parallel transport under the nccl backend): the library torch
     ships must load here and export every entry point the module calls, with the by-value ncclUniqueId of rccl.h:40-43."""

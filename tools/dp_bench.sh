@@ -9,7 +9,7 @@ for spec in "1 f32" "2 bf16" "3 bf16"; do
   python bench.py --full --config $1 --dtype $2 --force-dist --steps 20 --warmup 5 --no-cpu-baseline --timeline off \
       > $O/fd_c$1_$2.json 2> $O/fd_c$1_$2.err || echo "config $1 $2: rc=$?" >> $O/failures.txt
 done
-if [ "$1" != "" ] && [ "${DP_AB:-0}" = "1" ]; then
+if [ "${DP_AB:-0}" = "1" ]; then
   # A/B: the same collectives through torch.distributed's ProcessGroupNCCL (round 4's transport)
   export DRAM_TUNING=1 DRAM_DIST_TRANSPORT=torch
   for spec in "1 f32" "2 bf16" "3 bf16"; do
