@@ -282,6 +282,30 @@ class _ScanModule(_Base):
         scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=0.95, last_epoch=-1)
         return [optimizer], [scheduler]
 
+    def configure_gradient_clipping(self, optimizer, *positional, gradient_clip_val=None, gradient_clip_algorithm=None,
+                                    **_):
+        """Lightning's hook behind --gradient_clip_val / --gradient_clip_algorithm (the reference's
+        Trainer.add_argparse_args, train.py:46): instead of Lightning's in-place clip_gradients, which rewrites every
+        gradient in torch arithmetic in front of each step, the flags become the fused optimizer's attributes and the
+        clipping rides the update (optim.py); no gradient is rewritten.  Lightning 1.x passes optimizer_idx
+        positionally in front of the two keywords, 2.x the keywords alone; (value, algorithm) may also be given
+        positionally.  None or 0 switches clipping off, as in Lightning."""
+        if len(positional) == 2:
+            gradient_clip_val, gradient_clip_algorithm = positional
+        elif len(positional) > 2 or (positional and not isinstance(positional[0], int)):
+            raise TypeError("configure_gradient_clipping(optimizer[, optimizer_idx], gradient_clip_val=..., "
+                            "gradient_clip_algorithm=...)")
+        algorithm = getattr(gradient_clip_algorithm, "value", gradient_clip_algorithm) or "norm"
+        if algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', got {gradient_clip_algorithm!r}")
+        if not hasattr(optimizer, "max_grad_norm"):
+            raise TypeError("gradient clipping needs a fused optimizer (optim.FusedAdam / FusedSGD)")
+        val = None if gradient_clip_val is None or float(gradient_clip_val) == 0.0 else float(gradient_clip_val)
+        if val is not None and val < 0:
+            raise ValueError(f"gradient_clip_val must be >= 0, got {gradient_clip_val!r}")
+        optimizer.max_grad_norm = val if algorithm == "norm" else None
+        optimizer.clip_grad_value = val if algorithm == "value" else None
+
 
 class ScanCLSLightningModule(_ScanModule):
     """reference models.py:160-394 (train/val step part)."""

@@ -1417,3 +1417,42 @@ def adam_multi_dev(table: Tensor, chunks: Tensor, nchunks: int, hyper: Tensor):
 def sgd_multi(table: Tensor, chunks: Tensor, nchunks: int, lr, momentum, wd, first_step, grad_scale):
     _chk(_L().dram_sgd_multi(_p(table), _p(chunks), nchunks, lr, momentum, wd, int(first_step), grad_scale,
                              _stream()), "dram_sgd_multi")
+
+
+def _clip_arr(clip: Tensor) -> Tensor:
+    return _req(clip, "clip", shape=(4,))
+
+
+def grad_norm_multi(table: Tensor, chunks: Tensor, nchunks: int, partials: Tensor, clip: Tensor, grad_scale: float,
+                    hyper: Optional[Tensor] = None):
+    """clip[2] = |grad_scale| * ||g||_2 over every gradient of the table, clip[3] = min(1, clip[0] / (clip[2] + 1e-6));
+    partials: float64 scratch, one element per chunk; hyper given: grad_scale is read from hyper[5] on the device."""
+    _req(partials, "partials", dtype=torch.float64)
+    if partials.numel() < nchunks:
+        raise ValueError(f"partials: {nchunks} chunks need {nchunks} doubles, got {partials.numel()}")
+    if hyper is not None:
+        _req(hyper, "hyper", shape=(7,))
+    _chk(_L().dram_grad_norm_multi(_p(table), _p(chunks), nchunks, _p(partials), _p(_clip_arr(clip)), grad_scale,
+                                   _p(hyper), _stream()), "dram_grad_norm_multi")
+
+
+def grad_scale_multi(table: Tensor, chunks: Tensor, nchunks: int, clip: Tensor):
+    """IN PLACE g = g * clip[3] (clip[1] < 0) or clamp(g, -clip[1], clip[1]): the table's gradients are written."""
+    _chk(_L().dram_grad_scale_multi(_p(table), _p(chunks), nchunks, _p(_clip_arr(clip)), _stream()),
+         "dram_grad_scale_multi")
+
+
+def adam_multi_clip(table: Tensor, chunks: Tensor, nchunks: int, lr, b1, b2, eps, wd, bc1, bc2, grad_scale, clip: Tensor):
+    _chk(_L().dram_adam_multi_clip(_p(table), _p(chunks), nchunks, lr, b1, b2, eps, wd, bc1, bc2, grad_scale,
+                                   _p(_clip_arr(clip)), _stream()), "dram_adam_multi_clip")
+
+
+def adam_multi_dev_clip(table: Tensor, chunks: Tensor, nchunks: int, hyper: Tensor, clip: Tensor):
+    _req(hyper, "hyper", shape=(7,))
+    _chk(_L().dram_adam_multi_dev_clip(_p(table), _p(chunks), nchunks, _p(hyper), _p(_clip_arr(clip)), _stream()),
+         "dram_adam_multi_dev_clip")
+
+
+def sgd_multi_clip(table: Tensor, chunks: Tensor, nchunks: int, lr, momentum, wd, first_step, grad_scale, clip: Tensor):
+    _chk(_L().dram_sgd_multi_clip(_p(table), _p(chunks), nchunks, lr, momentum, wd, int(first_step), grad_scale,
+                                  _p(_clip_arr(clip)), _stream()), "dram_sgd_multi_clip")

@@ -60,6 +60,12 @@ def build_parser() -> ArgumentParser:
     # Lightning Trainer flag the reference exposes through Trainer.add_argparse_args (train.py:46): "bf16" runs the
     # step under autocast(bfloat16) there, the bf16 storage path here
     p.add_argument("--precision", default="32", type=str, choices=("32", "bf16"))
+    # ... and three more of them, with Lightning's names, defaults and semantics: clipping becomes the fused optimizer's
+    # max_grad_norm / clip_grad_value (no gradient is rewritten); the optimizer steps every accumulate_grad_batches
+    # batches and on the last batch of the epoch, each micro-batch's loss divided by that number
+    p.add_argument("--gradient_clip_val", default=None, type=float)
+    p.add_argument("--gradient_clip_algorithm", default="norm", type=str, choices=("norm", "value"))
+    p.add_argument("--accumulate_grad_batches", default=1, type=int)
     return p
 
 
@@ -158,7 +164,11 @@ def run_training_job(argv=None):
     module = module.to(device)
     if args.precision == "bf16":
         module.model.storage_dtype = torch.bfloat16
+    if args.accumulate_grad_batches < 1:
+        raise SystemExit("--accumulate_grad_batches must be >= 1")
     (optimizer,), (scheduler,) = module.configure_optimizers()
+    module.configure_gradient_clipping(optimizer, gradient_clip_val=args.gradient_clip_val,
+                                       gradient_clip_algorithm=args.gradient_clip_algorithm)
     start_epoch = 0
     found = find_checkpoint(ckp_path, args.ckp)
     if found is not None:
@@ -171,26 +181,34 @@ def run_training_job(argv=None):
     val_data = SyntheticSubtypeData(max(args.batch_size * world, args.num_samples // 4), args.batch_size, args.target_size,
                                     rank, world, device, args.seed + 7)
     augment = TrainAugment() if getattr(args, "augment", 0) else None        # models.py:66-74 (train mode only)
-    global_step = 0
+    global_step = 0                                # optimizer steps, as Lightning counts them
+    accumulate = args.accumulate_grad_batches
     best = (float("inf"), None)
     for epoch in range(start_epoch, args.max_epochs):
         module.train()
         running, step_outputs, losses = 0.0, [], []
+        optimizer.zero_grad(set_to_none=True)
         for i, batch in enumerate(data.epoch(epoch)):
             if augment is not None:
                 batch = augment_batch(batch, augment)
-            optimizer.zero_grad(set_to_none=True)
             out = module.training_step(batch, i)
-            out["loss"].backward()
-            optimizer.step()
+            # (under data parallel every micro-batch exchanges its gradients: there is no no_sync form)
+            (out["loss"] / accumulate if accumulate > 1 else out["loss"]).backward()
             losses.append(out["loss"].detach())
             step_outputs.append({k: v for k, v in out.items() if k != "loss"})
+            if (i + 1) % accumulate != 0 and i + 1 != len(data):
+                continue                           # gradients keep accumulating (zero_grad only after a step)
+            optimizer.step()
+            optimizer.zero_grad(set_to_none=True)
             global_step += 1
             if global_step % args.log_every_n_steps == 0:
                 running = float(out["loss"])
                 if rank == 0:
+                    # (the norm is read where the loss has just synchronised the host, and nowhere else)
+                    norm = (f" grad_norm {float(optimizer.last_grad_norm):.5f}"
+                            if optimizer.max_grad_norm is not None else "")
                     logging.info(f"epoch {epoch} step {global_step} train_loss {running:.5f} "
-                                 f"lr {optimizer.param_groups[0]['lr']:.3e}")
+                                 f"lr {optimizer.param_groups[0]['lr']:.3e}{norm}")
         # Lightning's fit loop: validation epoch, then the epoch-end hooks (gather + de-dup + class-weight update,
         # models.py:287-317 / :367-379), then the scheduler and ModelCheckpoint
         module.eval()

@@ -525,6 +525,34 @@ int dram_sgd_multi(const DramTensorRef* table, const DramChunkRef* chunks, int n
                    float momentum, float weight_decay, int first_step, float grad_scale,
                    dram_stream_t stream);
 
+/* Gradient clipping on the same work list (Lightning's --gradient_clip_val / --gradient_clip_algorithm, which the
+ * reference's Trainer.add_argparse_args puts on its command line, train.py:46,100).  clip = float[4] in device memory:
+ *   clip[0] in   max_norm
+ *   clip[1] in   clip_value; NEGATIVE selects norm mode in the launches below, >= 0 value mode
+ *   clip[2] out  total_norm = (float)(|grad_scale| * sqrt(sum g^2)), squares and sums in double
+ *   clip[3] out  coef = min(1, max_norm / (total_norm + 1e-6f)) in fp32 (torch.nn.utils.clip_grad_norm_)
+ * dram_grad_norm_multi: reads every gradient of the table once (4 B/element; p, m, v are not touched and may be NULL),
+ *   writes one double per chunk into partials[nchunks] and folds them in a second, one-block launch: a fixed summation
+ *   order that depends on the element index only -- not on the order the blocks ran in, and not on whether a gradient is
+ *   16- or only 4-byte aligned.  grad_scale: host value, or hyper[5] when hyper (dram_adam_multi_dev's block) is given.
+ * dram_*_clip: the three updates with gg = (g * grad_scale) * clip[3]  (norm mode)  or
+ *   gg = clamp(g * grad_scale, -clip[1], clip[1]) (value mode; a NaN stays a NaN) in place of g * grad_scale; everything
+ *   behind that is the code of the plain entry points.  No gradient is written.
+ * dram_grad_scale_multi: g = g * clip[3] or clamp(g, -clip[1], clip[1]) IN PLACE (8 B/element) -- the drop-in
+ *   clip_grad_norm_ / clip_grad_value_ for callers who look at the gradients afterwards. */
+int dram_grad_norm_multi(const DramTensorRef* table, const DramChunkRef* chunks, int nchunks, double* partials,
+                         float* clip, float grad_scale, const float* hyper, dram_stream_t stream);
+int dram_grad_scale_multi(const DramTensorRef* table, const DramChunkRef* chunks, int nchunks, const float* clip,
+                          dram_stream_t stream);
+int dram_adam_multi_clip(const DramTensorRef* table, const DramChunkRef* chunks, int nchunks, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
+                         float bias_corr2, float grad_scale, const float* clip, dram_stream_t stream);
+int dram_adam_multi_dev_clip(const DramTensorRef* table, const DramChunkRef* chunks, int nchunks, float* hyper,
+                             const float* clip, dram_stream_t stream);
+int dram_sgd_multi_clip(const DramTensorRef* table, const DramChunkRef* chunks, int nchunks, float lr,
+                        float momentum, float weight_decay, int first_step, float grad_scale, const float* clip,
+                        dram_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Deterministic input transforms of the reference data module (models.py:59-63):
  * IntensityWindow (functional.py:13-26), Standardize (intensity_transforms.py:108-111),
