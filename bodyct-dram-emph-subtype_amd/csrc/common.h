@@ -173,6 +173,30 @@ __device__ __forceinline__ void lin_src(int dst, float scale, int in, int& i0, i
   w0 = 1.f - w1;
 }
 
+// Nearest-neighbour sampling of a full-resolution mask on a coarser grid (head_loss.hip, cam.hip).
+// F.interpolate(mode='nearest') source index: min(floor(dst * in/out), in-1)
+__device__ __forceinline__ int nearest_src(int dst, float scale, int in) {
+  const int s = (int)floorf((float)dst * scale);
+  return s < in - 1 ? s : in - 1;
+}
+
+struct NearGeom {
+  int Dl, Hl, Wl;
+  float sz, sy, sx;
+};
+
+__device__ __forceinline__ long near_index(const NearGeom& n, long b, int z, int y, int x) {
+  return ((b * n.Dl + nearest_src(z, n.sz, n.Dl)) * n.Hl + nearest_src(y, n.sy, n.Hl)) * (long)n.Wl +
+         nearest_src(x, n.sx, n.Wl);
+}
+
+static inline NearGeom make_near(int Dl, int Hl, int Wl, int D, int H, int W) {
+  NearGeom n;
+  n.Dl = Dl; n.Hl = Hl; n.Wl = Wl;
+  n.sz = (float)Dl / (float)D; n.sy = (float)Hl / (float)H; n.sx = (float)Wl / (float)W;
+  return n;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

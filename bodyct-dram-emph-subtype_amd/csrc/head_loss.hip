@@ -7,22 +7,6 @@
 
 namespace {
 
-// F.interpolate(mode='nearest') source index: min(floor(dst * in/out), in-1)
-__device__ __forceinline__ int nearest_src(int dst, float scale, int in) {
-  const int s = (int)floorf((float)dst * scale);
-  return s < in - 1 ? s : in - 1;
-}
-
-struct NearGeom {
-  int Dl, Hl, Wl;
-  float sz, sy, sx;
-};
-
-__device__ __forceinline__ long near_index(const NearGeom& n, long b, int z, int y, int x) {
-  return ((b * n.Dl + nearest_src(z, n.sz, n.Dl)) * n.Hl + nearest_src(y, n.sy, n.Hl)) * (long)n.Wl +
-         nearest_src(x, n.sx, n.Wl);
-}
-
 // ----------------------------------------------------------------------------- head fwd
 template <int NOT, typename T>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
@@ -337,13 +321,6 @@ __global__ __launch_bounds__(256) void regloss_tail_kernel(RegTail a) {
     a.coef[3] = (float)((1.0 - alpha) / sw);
     a.coef[4] = a.coef[5] = a.coef[6] = a.coef[7] = 0.f;
   }
-}
-
-inline NearGeom make_near(int Dl, int Hl, int Wl, int D, int H, int W) {
-  NearGeom n;
-  n.Dl = Dl; n.Hl = Hl; n.Wl = Wl;
-  n.sz = (float)Dl / (float)D; n.sy = (float)Hl / (float)H; n.sx = (float)Wl / (float)W;
-  return n;
 }
 
 inline int head_blocks(long long vps) {

@@ -476,6 +476,26 @@ class Engine:
                 self._throttle()
             return self._forward(P, x, lungs, training, need_grad, dist, recompute, storage, need_x, need_param)
 
+    def forward_head(self, P: Dict[str, Tensor], x: Tensor, lungs: Optional[Tensor], training: bool, dist=None,
+                     storage=torch.float32):
+        """The no-grad forward, launch for launch, that also hands back what the heads read and what turns cotangents
+        of the outputs into the head kernels' operands: (dense_list, outs_list, kept) with kept = dict(xup3 [B,D,H,W,32]
+        in the storage type, hw / hb stacked head weights and bias, dense, lungs4, denom, n0, n1).  No tape is kept."""
+        if storage not in (torch.float32, torch.bfloat16):
+            raise NotImplementedError(f"activation storage type {storage}")
+        with ops.launch_scope(x.device):
+            return self._forward(P, x, lungs, training, False, dist, False, storage, keep_head=True)
+
+    def activation_map(self, kept: dict, g_dense: List[Optional[Tensor]], g_outs: List[Optional[Tensor]], method: str,
+                       relu: bool) -> Tensor:
+        """Class-activation map [B,D,H,W] at the us3 output of a forward_head(), for the score whose cotangents on
+        (dense_outs, outs) are given (conventions of backward): ops.cam on the operands head_bwd would get."""
+        sig = self.head == "reg"
+        with ops.launch_scope(kept["dense"].device):
+            gpool, gd = self._head_cotangents(kept, g_dense, g_outs)
+            return ops.cam(kept["xup3"], kept["hw"], kept["hb"], gd, gpool, kept["lungs4"] if sig else None, sig,
+                           method, relu)
+
     def backward(self, saved: dict, g_dense: List[Optional[Tensor]], g_outs: List[Optional[Tensor]]):
         with ops.launch_scope(saved["dense"].device):
             out = self._backward(saved, g_dense, g_outs)
@@ -558,7 +578,7 @@ class Engine:
             st.packed_ready.record(side)
 
     def _forward(self, P, x, lungs, training, need_grad, dist, recompute=False, storage=torch.float32, need_x=False,
-                 need_param=None):
+                 need_param=None, keep_head=False):
         st = _State(P, training, need_grad, dist, recompute, storage, need_x, need_param)
         B, _, D, H, W = x.shape
         shape_key = (tuple(x.shape), storage, x.device.index)
@@ -607,6 +627,8 @@ class Engine:
             saved = dict(st=st, x4=x4, y0=y0, xs=xs, mean0=mean0, invstd0=invstd0, count0=count0, ss0=ss0, amax=amax,
                          blocks=block_ctx, cu1=cu1, cu2=cu2, cu3=cu3, xup3=xup3, hw=hw, dense=dense, lungs4=lungs4,
                          denom=denom, n0=n0, n1=n1, xs_shape=tuple(xs.shape))
+        elif keep_head:                                 # forward_head: the heads' operands, nothing of the tape
+            saved = dict(xup3=xup3, hw=hw, hb=hb, dense=dense, lungs4=lungs4, denom=denom, n0=n0, n1=n1)
         if need_grad:
             self._conv_lists[shape_key] = list(st.convs)
             st.packed.clear()
@@ -614,14 +636,9 @@ class Engine:
             torch._foreach_add_(st.nbt, 1)               # one launch for all num_batches_tracked counters
         return dense_list, outs, saved
 
-    def _backward(self, saved, g_dense, g_outs):
-        st: _State = saved["st"]
-        dist = st.dist if st.need_param else None       # (no parameter gradient: nothing to reduce)
-        if dist is not None:
-            dist.begin_backward(saved["dense"].device)
-        if st.need_param and self._two_streams():
-            st.side = ops.side_stream(saved["dense"].device.index)
-
+    def _head_cotangents(self, saved, g_dense, g_outs):
+        """Cotangents of (dense_outs, outs) -> the head kernels' operands (gpool [B,NO], gdense [B,NO,D,H,W] or None):
+        the pooled scores are sums over the sample divided by `denom`, and the two heads are stacked."""
         n0, n1 = saved["n0"], saved["n1"]
         NO = n0 + n1
         dense = saved["dense"]
@@ -648,6 +665,21 @@ class Engine:
                 gd[:, :n0] = g_dense[0]
             if g_dense[1] is not None:
                 gd[:, n0:] = g_dense[1]
+        return gpool, gd
+
+    def _backward(self, saved, g_dense, g_outs):
+        st: _State = saved["st"]
+        dist = st.dist if st.need_param else None       # (no parameter gradient: nothing to reduce)
+        if dist is not None:
+            dist.begin_backward(saved["dense"].device)
+        if st.need_param and self._two_streams():
+            st.side = ops.side_stream(saved["dense"].device.index)
+
+        n0, n1 = saved["n0"], saved["n1"]
+        NO = n0 + n1
+        dense = saved["dense"]
+        sig = self.head == "reg"
+        gpool, gd = self._head_cotangents(saved, g_dense, g_outs)
         dxup3, wpart = ops.head_bwd(saved["xup3"], saved["hw"], dense if sig else None, gd, gpool,
                                     saved["lungs4"] if sig else None, sig)
         if st.need_param:

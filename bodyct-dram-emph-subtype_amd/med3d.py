@@ -23,6 +23,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
+from . import ops
 from .engine import ARCHS, EXPANSION, Engine
 
 __all__ = ["ResNetSegCls", "ResNetSegReg", "resnet18segcls", "resnet34segcls", "resnet50segcls",
@@ -270,6 +271,86 @@ class _ResNetSeg(nn.Module):
                     gs[i] = g.detach().float().contiguous()
             self._engine.backward(saved, dg, og)
         return saved["dx"]
+
+    def _forward_head(self, x, lungs):
+        """forward(x, lungs) as it runs under torch.no_grad(), keeping the heads' operands (engine.forward_head)."""
+        x = x.detach().contiguous().float()
+        if lungs is not None:
+            lungs = lungs.detach().contiguous().float()
+        with torch.no_grad():
+            return self._engine.forward_head(self._tensor_dict(), x, lungs, self.training, self._dist,
+                                             self._storage_now())[2]
+
+    def target_activations(self, x: torch.Tensor, lungs: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The output of get_target_layer() (us3: conv + BatchNorm + ReLU), the tensor the heads consume, of a forward in
+        the module's current mode run as forward() under torch.no_grad() runs it: [B,32,D/2,H/2,W/2] float32 (a permuted
+        view of the engine's NDHWC tensor; with bf16 storage the widened copy of what was stored)."""
+        self._check_input(x)
+        kept = self._forward_head(x, lungs)
+        with torch.no_grad(), ops.launch_scope(x.device):
+            return ops.cast(kept["xup3"], torch.float32).permute(0, 4, 1, 2, 3)
+
+    def activation_map(self, x: torch.Tensor, lungs: Optional[torch.Tensor] = None, *, out_grads=None, dense_grads=None,
+                       score=None, method: str = "gradcam", relu: bool = True,
+                       upsample_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Class-activation map of a score s at get_target_layer()'s output A ([B,V,32] per sample), G = ds/dA:
+            gradcam   r(sum_c alpha[b,c] A[b,v,c]),  alpha[b,c] = mean_v G[b,v,c]
+            hirescam  r(sum_c G[b,v,c] A[b,v,c])
+            layercam  r(sum_c max(G[b,v,c], 0) A[b,v,c])            r = ReLU if `relu` else identity
+        s is given by cotangents with input_gradient's conventions (out_grads / dense_grads: a pair each, tensor or
+        None), or by score=(head, index): outs[head][:, index] of every sample (index 0 or None for the reg networks).
+        Runs forward(x, lungs) in the module's current mode as under torch.no_grad() -- no tape, no .grad touched -- and
+        forms the map from A in one (hirescam, layercam) or two (gradcam) passes; G is never stored.  Returns
+        [B,1,D/2,H/2,W/2] float32, not normalised; with upsample_mask [B,Ds,Hs,Ws] the trilinear (align_corners=True)
+        up-sampling to that grid times the mask, [B,1,Ds,Hs,Ws].  Under distributed.attach the result is local to the rank."""
+        if method not in ops.CAM_METHODS:
+            raise ValueError(f"activation_map: unknown method {method!r} (one of {sorted(ops.CAM_METHODS)})")
+
+        def pair(gs, name):
+            gs = [None, None] if gs is None else list(gs)
+            if len(gs) != 2:
+                raise ValueError(f"{name}: expected two cotangents (or None), got {len(gs)}")
+            return gs
+
+        og, dg = pair(out_grads, "out_grads"), pair(dense_grads, "dense_grads")
+        reg = self.HEAD == "reg"
+        if score is not None:
+            if any(g is not None for g in og):
+                raise ValueError("activation_map: give score or out_grads, not both")
+            head, index = score
+            if head not in (0, 1):
+                raise ValueError(f"score: head must be 0 or 1, got {head!r}")
+            index = 0 if (reg and index is None) else index
+            if not isinstance(index, int) or not 0 <= index < self.n_classes[head]:
+                raise ValueError(f"score: index {index!r} is outside outs[{head}] ({self.n_classes[head]} columns)")
+        elif all(g is None for g in og + dg):
+            raise ValueError("activation_map: no score (out_grads, dense_grads and score are all None)")
+        if x.dim() == 5:                                # (anything else: _check_input raises below)
+            B, grid = x.shape[0], tuple(int(n) // 2 for n in x.shape[-3:])
+            out_shapes = [(B,) if reg else (B, n) for n in self.n_classes]
+            dense_shapes = [(B, n) + grid for n in self.n_classes]
+            for gs, shapes, name in ((og, out_shapes, "out_grads"), (dg, dense_shapes, "dense_grads")):
+                for i, (g, shape) in enumerate(zip(gs, shapes)):
+                    if g is not None and (not isinstance(g, torch.Tensor) or tuple(g.shape) != shape):
+                        raise ValueError(f"{name}[{i}]: expected a tensor of shape {shape}")
+            if upsample_mask is not None and (not isinstance(upsample_mask, torch.Tensor) or upsample_mask.dim() != 4
+                                              or upsample_mask.shape[0] != B):
+                raise ValueError("upsample_mask: expected a tensor [B,Ds,Hs,Ws]")
+        self._check_input(x)
+        for g in og + dg + [upsample_mask]:
+            if g is not None and g.device != x.device:
+                raise ValueError(f"activation_map: cotangents and upsample_mask must be on {x.device}")
+        if score is not None:
+            og[head] = torch.zeros(out_shapes[head], device=x.device)
+            og[head][..., index if not reg else slice(None)] = 1.0
+        kept = self._forward_head(x, lungs)
+        with torch.no_grad():
+            og, dg = ([None if g is None else g.detach().float().contiguous() for g in gs] for gs in (og, dg))
+            cam = self._engine.activation_map(kept, dg, og, method, bool(relu))
+            if upsample_mask is not None:
+                with ops.launch_scope(x.device):
+                    cam = ops.upproject(cam, upsample_mask.detach().float().contiguous(), tuple(upsample_mask.shape[1:]))[0]
+        return cam.unsqueeze(1)
 
 
 class ResNetSegCls(_ResNetSeg):

@@ -1348,6 +1348,50 @@ def head_bwd(x: Tensor, w: Tensor, dense: Optional[Tensor], gdense: Optional[Ten
     return dx, wpartial
 
 
+CAM_METHODS = {"gradcam": _lib.DRAM_CAM_GRADCAM, "hirescam": _lib.DRAM_CAM_HIRESCAM, "layercam": _lib.DRAM_CAM_LAYERCAM}
+
+
+def cam(x: Tensor, w: Tensor, bias: Tensor, gdense: Optional[Tensor], gpool: Tensor, lungs: Optional[Tensor],
+        sigmoid: bool, method: str = "gradcam", relu: bool = True) -> Tensor:
+    """Class-activation map at the target layer: x [B,D,H,W,32] (float32 or bfloat16) is the us3 output, w / bias the
+    stacked heads, (gdense, gpool, lungs, sigmoid) the cotangents exactly as head_bwd takes them -> [B,D,H,W] float32.
+    The layer gradient G = d score / d x is formed in registers from head_bwd's dpre and never stored.  hirescam /
+    layercam: one pass over x; gradcam: the block sums of dpre, their fold in double (reduce_partials), the combine pass."""
+    if method not in CAM_METHODS:
+        raise ValueError(f"cam: unknown method {method!r} (one of {sorted(CAM_METHODS)})")
+    sfx = _act(x, "x")
+    if x.dim() != 5 or x.shape[-1] != 32:
+        raise ValueError("cam: x must be the 32-channel us3 output [B,D,H,W,32]")
+    B, D, H, W, _ = x.shape
+    if min(B, D, H, W) < 1 or x.numel() >= 2 ** 31:
+        raise ValueError("cam: x must be non-empty and hold fewer than 2^31 elements")
+    NO = w.shape[0]
+    _req(w, "w", shape=(NO, 32))
+    _req(bias, "bias", shape=(NO,))
+    _req(gpool, "gpool", shape=(B, NO))
+    if gdense is not None:
+        _req(gdense, "gdense", shape=(B, NO, D, H, W))
+    Dl = Hl = Wl = 0
+    if lungs is not None:
+        _req(lungs, "lungs")
+        if lungs.dim() != 4 or lungs.shape[0] != B:
+            raise ValueError("cam: lungs must be [B,Dl,Hl,Wl]")
+        _, Dl, Hl, Wl = lungs.shape
+    out = torch.empty((B, D, H, W), device=x.device, dtype=torch.float32)
+    head = (_p(x), _p(w), _p(bias), _p(gdense), _p(gpool), _p(lungs), Dl, Hl, Wl)
+    if method != "gradcam":
+        _chk(_fn("dram_cam_point", sfx)(*head, _p(out), B, D, H, W, NO, int(sigmoid), CAM_METHODS[method], int(relu),
+                                        _stream()), "dram_cam_point")
+        return out
+    nblk = _L().dram_cam_nblk(D * H * W)
+    partial = torch.empty((nblk, B, NO), device=x.device, dtype=torch.float32)
+    _chk(_fn("dram_cam_sum", sfx)(*head, _p(partial), B, D, H, W, NO, int(sigmoid), _stream()), "dram_cam_sum")
+    sums = reduce_partials(partial)                     # [B, NO] float64; nblk <= 1 024: one block, no ticket word
+    _chk(_fn("dram_cam_combine", sfx)(_p(x), _p(w), _p(sums), _p(out), B, D, H, W, NO, int(relu), _stream()),
+         "dram_cam_combine")
+    return out
+
+
 def segloss_fwd(cle: Tensor, pse: Tensor, lungs: Tensor, ems: Tensor, binary: Tensor,
                 smoothness: float = 0.85) -> Tensor:
     """cle/pse [B,D,H,W]; lungs/ems [B,Dl,Hl,Wl]; binary [B] -> partial [nblk,6].  smoothness: the in-mask

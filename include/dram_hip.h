@@ -453,6 +453,30 @@ int dram_head_bwd(const float* x, const float* w, const float* dense, const floa
                   const float* gpool, const float* lungs, int Dl, int Hl, int Wl, float* dx,
                   float* wpartial, int B, int D, int H, int W, int NO, int sigmoid, dram_stream_t stream);
 
+/* Class-activation maps at the target layer (get_target_layer(), med3d.py:267,366: the us3 output x the heads read).
+ *   G[b][v][k] = sum_c w[c][k] * dpre[b][c][v], dpre exactly as dram_head_bwd defines it (gdense may be NULL; lungs as
+ *   for the heads), with s = sigmoid(bias[c] + w[c] . x) recomputed from x -- G is formed in registers, never stored.
+ *   out [B][D*H*W] float; r(t) = relu != 0 ? max(t, 0) : t.
+ * dram_cam_point (one pass over x):  DRAM_CAM_HIRESCAM  out = r(sum_k G * x)
+ *                                    DRAM_CAM_LAYERCAM  out = r(sum_k max(G, 0) * x)
+ * DRAM_CAM_GRADCAM, out = r(sum_k alpha[b][k] * x), alpha[b][k] = (1/V) sum_v G[b][v][k], is two passes:
+ *   dram_cam_sum      partial [nblk][B][NO], nblk = dram_cam_nblk(D*H*W): per-block sums of dpre (x is read only when
+ *                     sigmoid != 0); the caller folds them with dram_fold_partials (R*C = B*NO: samples stay apart)
+ *   dram_cam_combine  sums [B][NO] (double): alpha = (sum_c w[c][k] * sums[b][c]) / (D*H*W) in double, then the map.
+ * Fixed summation order, no atomics: bit-identical from call to call.  B*D*H*W*32 < 2^31 (DRAM_ERR_UNSUPPORTED). */
+#define DRAM_CAM_GRADCAM 0
+#define DRAM_CAM_HIRESCAM 1
+#define DRAM_CAM_LAYERCAM 2
+int dram_cam_nblk(long long voxels_per_sample);
+int dram_cam_point(const float* x, const float* w, const float* bias, const float* gdense, const float* gpool,
+                   const float* lungs, int Dl, int Hl, int Wl, float* out, int B, int D, int H, int W, int NO,
+                   int sigmoid, int method, int relu, dram_stream_t stream);
+int dram_cam_sum(const float* x, const float* w, const float* bias, const float* gdense, const float* gpool,
+                 const float* lungs, int Dl, int Hl, int Wl, float* partial, int B, int D, int H, int W, int NO,
+                 int sigmoid, dram_stream_t stream);
+int dram_cam_combine(const float* x, const float* w, const double* sums, float* out, int B, int D, int H, int W,
+                     int NO, int relu, dram_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* dRAM segmentation losses -- models.py:523-531 + metrics.py:10-37, label prep
  * models.py:567-570.  cle/pse: [B,1,D,H,W] dense maps; lungs/ems: full-res masks
@@ -684,6 +708,14 @@ int dram_head_fwd_bf16(const void* x, const float* w, const float* bias, const f
 int dram_head_bwd_bf16(const void* x, const float* w, const float* dense, const float* gdense, const float* gpool,
                        const float* lungs, int Dl, int Hl, int Wl, void* dx, float* wpartial, int B, int D, int H, int W,
                        int NO, int sigmoid, dram_stream_t stream);
+int dram_cam_point_bf16(const void* x, const float* w, const float* bias, const float* gdense, const float* gpool,
+                        const float* lungs, int Dl, int Hl, int Wl, float* out, int B, int D, int H, int W, int NO,
+                        int sigmoid, int method, int relu, dram_stream_t stream);
+int dram_cam_sum_bf16(const void* x, const float* w, const float* bias, const float* gdense, const float* gpool,
+                      const float* lungs, int Dl, int Hl, int Wl, float* partial, int B, int D, int H, int W, int NO,
+                      int sigmoid, dram_stream_t stream);
+int dram_cam_combine_bf16(const void* x, const float* w, const double* sums, float* out, int B, int D, int H, int W,
+                          int NO, int relu, dram_stream_t stream);
 
 #ifdef __cplusplus
 }
