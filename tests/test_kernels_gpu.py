@@ -105,6 +105,11 @@ C1_CASES = [
     (2, 8, 8, 8, 128, 256),
     (1, 8, 16, 16, 256, 64),
     (1, 8, 16, 32, 512, 192),           # Cout only a multiple of 64; the weight gradient splits over voxels
+    # the (Cout, Cin) tile forms of the weight-gradient GEMM that the cases above do not launch from this entry point
+    (1, 4, 8, 8, 128, 128),             # 128 x 128
+    (1, 4, 8, 8, 256, 256),             # 256 x 256
+    (1, 4, 8, 8, 256, 128),             # 128 x 256
+    (1, 4, 8, 8, 64, 256),              # 256 x 64
 ]
 
 
@@ -200,6 +205,7 @@ WINO_CASES = [
     (1, 8, 16, 16, 256, 256, 4),        # layer3/4-like: 256-column tiles, dilation 4
     (2, 4, 8, 8, 192, 320, 1),          # channel counts that are only multiples of 64
     (1, 2, 5, 3, 64, 64, 4),            # dilation > extent: EMPTY residue sub-lattices (tiles whose origin lies outside)
+    (1, 4, 4, 4, 256, 128, 1),          # TN GEMM, 128 x 256 tiles (Cout x Cin): the one form no case above launches
 ]
 
 
