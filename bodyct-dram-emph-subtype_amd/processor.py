@@ -17,6 +17,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
+from . import transforms
 from .models import CLE_RATIO_MAP, PSE_RATIO_MAP
 from .ops import _L, _chk, _p, _req, _stream
 
@@ -73,6 +74,18 @@ def build_outputs(predictions: List[dict], want_u8: bool = True) -> List[dict]:
             results.append({"entity": uid, "metrics": metrics, "error_messages": [], "full_cle": vols["cle"],
                             "full_pse": vols["pse"]})
     return results
+
+
+def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[float], target_size: Sequence[int],
+                 uid=None, want_u8: bool = True, **prepare_kw) -> dict:
+    """One scan + its lobe segmentation -> its entry of ``build_outputs``: ``transforms.prepare_case`` (dataset.py:57-92)
+    -> ``transforms.prepare_sample(target_size)`` -> a batch of one -> ``module.predict_step`` -> ``build_outputs``.
+    The composition only; `prepare_kw` goes to ``prepare_case`` (crop_border, dilate_iterations, ...)."""
+    case = transforms.prepare_case(scan, lobes, spacing, uid=uid, **prepare_kw)
+    sample = transforms.prepare_sample(case, target_size)
+    batch = {k: sample[k].unsqueeze(0) for k in ("image", "lung_mask", "ess_mask", "crop_slice", "original_size")}
+    batch["uid"] = [uid]
+    return build_outputs([module.predict_step(batch, 0)], want_u8=want_u8)[0]
 
 
 def write_reports(results: List[dict], centrilobular_json: Optional[str] = None, paraseptal_json: Optional[str] = None,

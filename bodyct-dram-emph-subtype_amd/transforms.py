@@ -16,6 +16,7 @@ if not __package__:          # imported top-level (this directory on sys.path): 
     __package__ = _dropin.adopt(__name__)
 
 import ctypes
+import math
 import random
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -78,6 +79,83 @@ def prepare_sample(sample: Dict[str, torch.Tensor], target_size: Sequence[int]) 
             out[k] = prepare_image(v, target_size)
         elif k.endswith("_mask"):
             out[k] = prepare_mask(v, target_size)
+    return out
+
+
+# --------------------------------------------------------------------------- scan + lobes -> prepared predict case
+def _lobes_operand(lobes: torch.Tensor):
+    """(tensor the kernels read, its lobe_dtype code): uint8 / bool and int16 volumes are read as they are, anything
+    else is reduced to its `> 0` mask first (one torch pass)."""
+    if lobes.dtype == torch.bool:
+        lobes = lobes.contiguous().view(torch.uint8)
+    elif lobes.dtype not in (torch.uint8, torch.int16):
+        lobes = (lobes > 0).view(torch.uint8)
+    lobes = lobes.contiguous()
+    if lobes.data_ptr() % 16:                   # dram_lung_bbox reads 16-byte vectors
+        lobes = lobes.clone()
+    return lobes, (2 if lobes.dtype == torch.int16 else 1)
+
+
+def prepare_case(scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[float], crop_border: float = 5,
+                 dilate_iterations: int = 2, fill_value: int = -2048, ess_threshold: int = -910,
+                 want_original: bool = False, uid=None) -> Dict[str, object]:
+    """The reference's ``SubtypingInference.get_data`` (dataset.py:57-92) with ``utils.find_crops`` (utils.py:53-63) on
+    the device: lung = lobes > 0; the scan outside ``dilate_iterations`` dilations of the lung (full 3x3x3 structure)
+    is set to ``fill_value``; scan, lung and (``want_original``) the untouched scan are cropped to the lung's bounding
+    box padded by ``ceil(crop_border / spacing)`` voxels per axis and clipped to the volume (``crop_border <= 0``: the
+    tight box); ess_mask = (scan < ess_threshold) & lung.
+
+    scan, lobes: device tensors [D,H,W]; spacing in array-axis order (z, y, x), as the reference's ``read_image``
+    returns it.  A scan that is not int16 is converted with ``.to(torch.int16)`` first (the reference's
+    ``astype(np.int16)``) and the threshold applies to the converted values.  Returns the reference's keys: 'image'
+    int16, 'lung_mask' / 'ess_mask' bool, 'original_image' int16 (only when asked), 'crop_slice' int64 [3,2] and
+    'original_size' int64 [3] (host tensors), 'uid'.  The dict feeds ``prepare_sample`` unchanged.
+
+    The bounding box is read back to the host once per case, because the sizes of the outputs depend on it: the call
+    synchronises with the device and cannot be captured into a hipGraph.  Raises IndexError for an empty lung (as
+    the reference's ``find_objects(...)[0]`` does) and ValueError when scan and lobes differ in shape."""
+    for t, name in ((scan, "scan"), (lobes, "lobes")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"prepare_case: {name}: expected a device tensor (libdram_hip has no CPU path)")
+    if scan.dim() != 3 or tuple(scan.shape) != tuple(lobes.shape):
+        raise ValueError(f"prepare_case: scan {tuple(scan.shape)} and lobes {tuple(lobes.shape)} must be one [D,H,W] shape")
+    if scan.numel() >= 2 ** 31:
+        raise ValueError("prepare_case: volumes of 2^31 voxels or more are not supported")
+    r = int(dilate_iterations)
+    if not 0 <= r <= 3:
+        raise ValueError("prepare_case: dilate_iterations must be 0..3")
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3:
+        raise ValueError("prepare_case: spacing must have three entries (z, y, x)")
+    scan = scan.to(torch.int16).contiguous()
+    _req(scan, "scan", torch.int16)
+    lobes, code = _lobes_operand(lobes)
+    _req(lobes, "lobes", lobes.dtype)
+    D, H, W = (int(v) for v in scan.shape)
+    dev = scan.device
+    partial = torch.empty((_L().dram_lung_bbox_nblk(scan.numel()), 8), device=dev, dtype=torch.int32)
+    box = torch.empty((8,), device=dev, dtype=torch.int32)
+    _chk(_L().dram_lung_bbox(_p(lobes), code, _p(partial), _p(box), D, H, W, _stream()), "dram_lung_bbox")
+    b = box.tolist()                                              # the one host read-back
+    if b[6] == 0:
+        raise IndexError("prepare_case: the lobe segmentation holds no lung voxel")
+    sl = []
+    for (lo, hi), size, s in zip((b[0:2], b[2:4], b[4:6]), (D, H, W), sp):
+        pad = int(math.ceil(crop_border / s)) if crop_border > 0 else 0
+        sl.append((max(0, lo - pad), min(size, hi + pad)))
+    (z0, z1), (y0, y1), (x0, x1) = sl
+    shape = (z1 - z0, y1 - y0, x1 - x0)
+    image = torch.empty(shape, device=dev, dtype=torch.int16)
+    lung = torch.empty(shape, device=dev, dtype=torch.uint8)
+    ess = torch.empty(shape, device=dev, dtype=torch.uint8)
+    orig = torch.empty(shape, device=dev, dtype=torch.int16) if want_original else None
+    _chk(_L().dram_case_prepare(_p(scan), _p(lobes), code, _p(image), _p(lung), _p(ess), _p(orig), D, H, W, z0, y0, x0,
+                                *shape, r, int(fill_value), int(math.ceil(ess_threshold)), _stream()), "dram_case_prepare")
+    out = {"image": image, "lung_mask": lung.view(torch.bool), "ess_mask": ess.view(torch.bool),
+           "crop_slice": torch.tensor(sl, dtype=torch.int64), "original_size": torch.tensor([D, H, W], dtype=torch.int64),
+           "uid": uid}
+    if want_original:
+        out["original_image"] = orig
     return out
 
 

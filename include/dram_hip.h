@@ -598,6 +598,27 @@ int dram_prep_mask(const float* mask, const int* zidx, float* out, int D, int H,
 int dram_resample_paste(const float* src, float* out_f32, uint8_t* out_u8, int D, int H, int W, int rd, int rh, int rw,
                         int oz, int oy, int ox, int Do, int Ho, int Wo, dram_stream_t stream);
 
+/* Scan + lobe segmentation -> prepared predict case (dataset.py:57-92 SubtypingInference.get_data with
+ * utils.py:53-63 find_crops), csrc/case_prep.hip.  scan [D,H,W] int16 HU; lobes [D,H,W] of lobe_dtype 1 (uint8) or
+ * 2 (int16), 16-byte aligned for dram_lung_bbox; lung = lobes > 0.  D*H*W < 2^31 (DRAM_ERR_UNSUPPORTED).
+ *   dram_lung_bbox: partial [dram_lung_bbox_nblk(D*H*W)][8] int32 scratch (every row is written: no memset), then a
+ *     fixed-order fold -> box [8] int32 (device) = {z0, z1, y0, y1, x0, x1, voxel count, 0}, half-open; all 0 for
+ *     an empty lung.  No atomics: bit-identical from call to call.
+ *   dram_case_prepare over the crop box [Dc,Hc,Wc] at offset (z0,y0,x0), which must lie inside the volume AND hold
+ *     every lung voxel (the padded bounding box does; lobes outside it are not read, so the dilation needs no halo
+ *     from outside the crop):
+ *       image [Dc,Hc,Wc] int16 = scan where the (2*radius+1)^3 box dilation of the lung, clipped to the volume,
+ *         is set (= `radius` iterations of scipy's binary_dilation with the full 3x3x3 structure), else fill_value;
+ *       lung_mask, ess_mask [Dc,Hc,Wc] uint8 0/1, ess = scan < threshold && lung;
+ *       original (optional, may be NULL) int16 = the plain crop of scan.
+ *     radius 0..3; fill_value and threshold within int16.  The dilated volume is never written. */
+int dram_lung_bbox_nblk(long long n);
+int dram_lung_bbox(const void* lobes, int lobe_dtype, int* partial, int* box, int D, int H, int W,
+                   dram_stream_t stream);
+int dram_case_prepare(const void* scan, const void* lobes, int lobe_dtype, void* image, uint8_t* lung_mask,
+                      uint8_t* ess_mask, void* original, int D, int H, int W, int z0, int y0, int x0, int Dc, int Hc,
+                      int Wc, int radius, int fill_value, int threshold, dram_stream_t stream);
+
 /* Train-time augmentations (models.py:66-74) with GIVEN parameters, fused into one gather pass:
  * GaussianAddictive (intensity_transforms.py:145-177; noise [D,H,W] supplied by the caller, minmax[2] = volume
  * {min, max} on the device, e.g. folded from dram_minmax partials [nblk][2]), BoxMaskOut (:180-237), Flip
