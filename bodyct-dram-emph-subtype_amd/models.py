@@ -5,8 +5,10 @@ surface for the train / predict path -- ``forward``, ``training_step``, ``shared
 ``predict_step``, ``configure_optimizers`` -- on top of the HIP engine.  When
 ``pytorch_lightning`` is importable they subclass ``pl.LightningModule`` (so
 ``Trainer.fit`` / ``processor.py`` work unchanged); otherwise a plain ``nn.Module`` with the
-same methods (this image has no Lightning).  Epoch-end reporting, plotting and csv dumps
-(models.py:278-379, :594-682) are out of scope.
+same methods (this image has no Lightning).  The validation / test activation-map panels of
+``_draw_predictions`` (models.py:192-234, :455-493) are ``draw_predictions`` / ``heat_volumes`` below, switched on by
+``args.draw_predictions``; the confusion-matrix plots and csv dumps of the epoch-end hooks (models.py:278-379,
+:594-682) are out of scope.
 
 The dRAM losses (models.py:512-531 + metrics.py) run as fused HIP kernels
 (csrc/head_loss.hip) behind ``torch.autograd.Function``; O(B) scalar algebra stays in torch.
@@ -17,9 +19,11 @@ if not __package__:          # imported top-level (this directory on sys.path): 
     import _dropin
     __package__ = _dropin.adopt(__name__)
 
+import os
 from types import SimpleNamespace
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -209,7 +213,115 @@ def update_class_weights(weights: torch.Tensor, y_true: torch.Tensor, y_pred: to
     return (w / w.sum()).to(weights.dtype).cpu()
 
 
+# --------------------------------------------------------------------------- activation-map panels (_draw_predictions)
+def _jet_table() -> np.ndarray:
+    """The 256 x 3 uint8 RGB 'jet' map from the usual piecewise-linear formula: channel = clip(1.5 - |4 v - k|, 0, 1)
+    with k = 3, 2, 1 for red, green, blue and v = i / 255."""
+    v = np.arange(256, dtype=np.float64) / 255.0
+    rgb = [np.clip(1.5 - np.abs(4.0 * v - k), 0.0, 1.0) for k in (3.0, 2.0, 1.0)]
+    return np.floor(np.stack(rgb, axis=1) * 255.0 + 0.5).astype(np.uint8)
+
+
+JET = _jet_table()
+
+
+def _lung_bytes(lungs: torch.Tensor) -> torch.Tensor:
+    """[B,D,H,W] or [B,1,D,H,W] mask -> contiguous uint8 [B,D,H,W]; bool / uint8 are read as they are (non-zero =
+    lung), anything else is reduced with != 0."""
+    if lungs.dim() == 5 and lungs.shape[1] == 1:
+        lungs = lungs[:, 0]
+    if lungs.dim() != 4:
+        raise ValueError(f"lungs must be [B,D,H,W] or [B,1,D,H,W], got {tuple(lungs.shape)}")
+    if lungs.dtype == torch.bool:
+        return lungs.contiguous().view(torch.uint8)
+    if lungs.dtype != torch.uint8:
+        return (lungs != 0).view(torch.uint8)
+    return lungs.contiguous()
+
+
+def heat_volumes(dense_outs, lungs, head: str, *, zsel=None, want_f32: bool = False, want_u8: bool = True) -> dict:
+    """The CLE and PSE heat volumes of the reference's ``_draw_predictions`` on the scan grid, from the dense head
+    outputs ``dense_outs = (cle [B,C0,d,h,w], pse [B,C1,d,h,w])`` of ``module.forward`` and the lung mask
+    ([B,D,H,W] or [B,1,D,H,W] with (D,H,W) = (2d,2h,2w); bool / uint8, a float mask is reduced with ``!= 0``):
+
+      head "cls" (models.py:201-229)  sum_{c>=1} relu(up_c) / (its maximum over the volume + 1e-7) * lung
+      head "reg" (models.py:464-488)  up_0 * lung
+
+    with up = F.interpolate(dense, size=(D,H,W), mode='trilinear').  Fused HIP passes (csrc/heat.hip): the up-sampled
+    channels are never written.  ``zsel`` [B,nz]: only those output z slices, [B,nz,H,W], bit-identical to the slices
+    of the full volume.  -> {"cle": t, "pse": t}; t is the uint8 volume trunc(255 clamp(v, 0, 1)) (``want_u8``), the
+    unclamped float32 volume (``want_f32``), or the pair (f32, u8) when both are asked for."""
+    if head not in ("cls", "reg"):
+        raise ValueError(f"heat_volumes: head must be 'cls' or 'reg', got {head!r}")
+    if len(dense_outs) != 2:
+        raise ValueError("heat_volumes: dense_outs is the pair (cle, pse) of module.forward")
+    lung = _lung_bytes(lungs)
+    out = {}
+    for name, d in zip(("cle", "pse"), dense_outs):
+        d = d.detach()
+        if head == "cls":
+            f32, u8 = ops.heat_volume(d, lung, "classsum", ops.heat_peak(d), zsel, want_f32, want_u8)
+        else:
+            f32, u8 = ops.heat_volume(d, lung, "plain", None, zsel, want_f32, want_u8)
+        out[name] = (f32, u8) if (want_f32 and want_u8) else (u8 if want_u8 else f32)
+    return out
+
+
+def panel_slices(z0: int, z1: int, D: int, num_slices: int = 5) -> Optional[List[int]]:
+    """The slices ``draw_mask_tile_singleview_heatmap`` (utils.py:125-127, :157-167) shows for ``coord_axis=0`` and its
+    default ``flip_axis=0``, from the lung's half-open z extent [z0, z1) in a volume of D slices.  In the flipped
+    frame the lung spans s = D - z1 .. e = D - z0 and every (e - s) // num_slices-th slice from s is taken; a lung
+    thinner than num_slices falls back to the whole volume (s, e = 0, D - 1), and a stride that is still 0 raises
+    ValueError (the reference's ``range(s, e, 0)`` does).  Returns ORIGINAL z indices in display order (the flipped
+    frame's, i.e. descending), or None for an empty lung (z1 <= z0: the reference prints "no object found!")."""
+    if z1 <= z0:
+        return None
+    s, e = D - z1, D - z0
+    stride = (e - s) // num_slices
+    if stride == 0:
+        s, e = 0, D - 1
+        stride = (e - s) // num_slices
+    if stride == 0:
+        raise ValueError(f"panel_slices: {D} slices cannot show {num_slices} (range() arg 3 must not be zero)")
+    return [D - 1 - k for k in list(range(s, e, stride))[:num_slices]]
+
+
+def sheet_from_panels(panels: np.ndarray) -> np.ndarray:
+    """panels uint8 [5, num, H, W] (scan, lung, CLE heat, PSE heat, LAA-950) -> the tile sheet uint8 [5 H, num W, 3]
+    (RGB): one column per slice; row 1 the scan slice in grey, rows 2-5 the jet-coloured mask blended half and half
+    over it, (JET[mask] + grey + 1) >> 1.  No zoom, titles or padding (differences from the reference's JPG:
+    INTEGRATION.md)."""
+    panels = np.asarray(panels)
+    if panels.dtype != np.uint8 or panels.ndim != 4:
+        raise ValueError("sheet_from_panels: panels must be uint8 [rows, num, H, W]")
+    grey = panels[0].astype(np.uint16)[..., None]                         # [num, H, W, 1]
+    rows = [np.repeat(panels[0][..., None], 3, axis=-1)]
+    rows += [((JET[m].astype(np.uint16) + grey + 1) >> 1).astype(np.uint8) for m in panels[1:]]
+    return np.concatenate([np.concatenate(list(r), axis=1) for r in rows], axis=0)
+
+
+def _window_minmax_u8(sel: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor) -> torch.Tensor:
+    """utils.windowing(scan, from_span=None).astype(np.uint8) on the selected slices, in the reference's float32
+    operation order: clip, (x - min) / (max - min) * 255, truncate.  A constant volume (max == min) gives zeros where
+    the reference divides 0 by 0."""
+    rng = mx - mn
+    q = (torch.minimum(torch.maximum(sel, mn), mx) - mn) / rng * 255.0
+    return torch.where(rng > 0, q, torch.zeros_like(q)).to(torch.uint8)
+
+
+def _save_sheet(path_stem: str, sheet: np.ndarray) -> str:
+    try:
+        from matplotlib.image import imsave
+    except Exception:  # noqa: BLE001  (no matplotlib: keep the pixels)
+        np.save(path_stem + ".npy", sheet)
+        return path_stem + ".npy"
+    imsave(path_stem + ".png", sheet)
+    return path_stem + ".png"
+
+
 class _ScanModule(_Base):
+    _head = None          # "cls" | "reg": which maps _draw_predictions draws (set by the two modules)
+
     def __init__(self, args):
         self.args = args
         super().__init__()
@@ -232,6 +344,93 @@ class _ScanModule(_Base):
 
     def test_step(self, batch, batch_idx):
         return self.shared_step(batch, batch_idx, TEST_PHASE)
+
+    # ---- activation-map panels (models.py:192-234 / :455-493) ----------------------------------------------
+    def heat_volumes(self, dense_outs, lungs, **kw) -> dict:
+        """``heat_volumes`` for this module's networks: the volumes themselves, e.g. to save next to
+        ``predict_case``'s output."""
+        return heat_volumes(dense_outs, lungs, self._head, **kw)
+
+    def draw_predictions(self, batch, dense_outs, pred_cle, pred_pse, stage, batch_idx=0, epoch=0, root=None,
+                         num_slices=5):
+        """The reference's ``_draw_predictions``: per sample the five uint8 volumes it hands to
+        ``draw_mask_tile_singleview_heatmap`` -- windowed scan, lung * 255, CLE heat, PSE heat, em * 255 -- at the
+        ``num_slices`` slices that function shows (``panel_slices``), and the tile sheet.  Returns a list of
+        dict(uid, z, panels, sheet, path): ``panels`` uint8 [5, num, H, W] and ``sheet`` uint8 [5 H, num W, 3] on the
+        host, ``z`` the original slice indices in display order; all None but ``uid`` for an empty lung.  With ``root``
+        the sheet is written to ``root/debug_input_data/<epoch>/<stage>/<uid>_label_<cle>_<predcle>_<pse>_<predpse>.png``
+        (``.npy`` without matplotlib).  ``uid`` is the batch's 'uid' entry, else its 'index'.
+
+        Only the shown slices of the heat volumes are computed and written (``heat_volumes(..., zsel=...)``); the scan's
+        min / max come from one reduction pass, the windowing of the shown slices is float32 torch glue in the
+        reference's operation order.  A constant scan gives a zero row where the reference gives NaN.  The lung's z
+        extent (dram_lung_bbox) is read back once per drawn batch, so this path synchronises with the device and
+        cannot be captured into a hipGraph."""
+        from .transforms import _L, _chk, _p, _stream
+        with torch.no_grad():
+            scans = batch["image"].float().contiguous()
+            lung = _lung_bytes(batch["lung_mask"])
+            ems = batch["em_mask"]
+            B, D, H, W = lung.shape
+            if tuple(scans.shape) != (B, D, H, W) or tuple(ems.shape) != (B, D, H, W):
+                raise ValueError("draw_predictions: image, lung_mask and em_mask must share one [B,D,H,W] shape")
+            dev = lung.device
+            lib = _L()
+            boxes = torch.empty((B, 8), device=dev, dtype=torch.int32)
+            part = torch.empty((lib.dram_lung_bbox_nblk(D * H * W), 8), device=dev, dtype=torch.int32)
+            mm = []
+            for b in range(B):
+                lb = lung[b] if lung[b].data_ptr() % 16 == 0 else lung[b].clone()    # the bbox pass reads 16-byte vectors
+                ops._req(lb, "lung_mask", torch.uint8)
+                _chk(lib.dram_lung_bbox(_p(lb), 1, _p(part), _p(boxes[b]), D, H, W, _stream()), "dram_lung_bbox")
+                ops._req(scans[b], "image")
+                mp = torch.empty((lib.dram_minmax_nblk(D * H * W), 2), device=dev, dtype=torch.float32)
+                _chk(lib.dram_minmax(_p(scans[b]), _p(mp), D * H * W, _stream()), "dram_minmax")
+                mm.append((mp[:, 0].amin(), mp[:, 1].amax()))                         # O(nblk) glue
+            zs = [panel_slices(z0, z1, D, num_slices) for z0, z1, *_ in boxes.tolist()]   # the one host read-back
+            nz = max((len(z) for z in zs if z is not None), default=0)
+            uids = batch["uid"] if batch.get("uid") is not None else batch["index"].reshape(-1).tolist()
+            results = [dict(uid=uids[b], z=zs[b], panels=None, sheet=None, path=None) for b in range(B)]
+            if nz == 0:
+                return results
+            zsel = [z if z is not None else [0] * nz for z in zs]
+            heat = heat_volumes(dense_outs, lung, self._head, zsel=zsel)
+            labels = [t.reshape(-1).tolist() for t in (batch["cls_label"], pred_cle, batch["pse_label"], pred_pse)]
+            for b, z in enumerate(zs):
+                if z is None:
+                    continue
+                zi = torch.tensor(z, device=dev)
+                rows = [_window_minmax_u8(scans[b][zi], *mm[b]), (lung[b][zi] != 0).to(torch.uint8) * 255,
+                        heat["cle"][b], heat["pse"][b], (ems[b][zi].float() * 255.0).to(torch.uint8)]
+                panels = torch.stack(rows).cpu().numpy()
+                res = results[b]
+                res["panels"], res["sheet"] = panels, sheet_from_panels(panels)
+                if root is not None:
+                    folder = os.path.join(str(root), "debug_input_data", str(epoch), str(stage))
+                    os.makedirs(folder, exist_ok=True)
+                    cle, pcle, pse, ppse = (col[b] for col in labels)
+                    res["path"] = _save_sheet(os.path.join(folder, f"{res['uid']}_label_{cle}_{pcle}_{pse}_{ppse}"),
+                                              res["sheet"])
+            return results
+
+    def _maybe_draw(self, batch, batch_idx, stage, dense_outs, out):
+        """models.py:266-272: the first ``args.draw_predictions`` validation / test batches, on rank 0 (the reference
+        hard-codes 50; the default 0 draws nothing)."""
+        if stage == TRAIN_PHASE or not int(getattr(self.args, "draw_predictions", 0) or 0) > batch_idx:
+            return
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank():
+            return
+        self.draw_predictions(batch, dense_outs, out["pred_cle_labels"], out["pred_pse_labels"], stage, batch_idx,
+                              epoch=self._draw_epoch(), root=getattr(self.args, "model_path", None))
+
+    def _draw_epoch(self):
+        """models.py:194-197: ``epoch_number`` when the caller set one (train.py does), else the trainer's epoch"""
+        if hasattr(self, "epoch_number"):
+            return self.epoch_number
+        try:
+            return int(self.current_epoch)
+        except Exception:  # noqa: BLE001  (no Lightning, or no trainer attached)
+            return 0
 
     # ---- epoch end (models.py:287-317 / :603-633, :367-379) ------------------------------------------------
     def training_epoch_end(self, step_outputs):
@@ -309,6 +508,7 @@ class _ScanModule(_Base):
 
 class ScanCLSLightningModule(_ScanModule):
     """reference models.py:160-394 (train/val step part)."""
+    _head = "cls"
 
     def shared_step(self, batch, batch_idx, stage):
         with torch.set_grad_enabled(stage == TRAIN_PHASE):
@@ -327,11 +527,14 @@ class ScanCLSLightningModule(_ScanModule):
                     self.log(f"{TRAIN_PHASE}_{k}", v, on_step=True, on_epoch=True, prog_bar=True)
                 self.log(f"{TRAIN_PHASE}_loss", loss, on_step=True, on_epoch=True, prog_bar=True)
                 out["loss"] = loss
+            else:
+                self._maybe_draw(batch, batch_idx, stage, dense_outs, out)
             return out
 
 
 class ScanRegLightningModule(_ScanModule):
     """reference models.py:397-698 (train/val/predict step part)."""
+    _head = "reg"
 
     def __init__(self, args):
         super().__init__(args)
@@ -357,6 +560,8 @@ class ScanRegLightningModule(_ScanModule):
                     self.log(f"{TRAIN_PHASE}_{k}", v, on_step=True, on_epoch=True, prog_bar=True)
                 self.log(f"{TRAIN_PHASE}_loss", loss, on_step=True, on_epoch=True, prog_bar=True)
                 out["loss"] = loss
+            else:
+                self._maybe_draw(batch, batch_idx, stage, dense_outs, out)
             return out
 
     def predict_step(self, batch, batch_idx: int, dataloader_idx: int = 0):

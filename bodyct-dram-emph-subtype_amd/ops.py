@@ -1392,6 +1392,98 @@ def cam(x: Tensor, w: Tensor, bias: Tensor, gdense: Optional[Tensor], gpool: Ten
     return out
 
 
+HEAT_MODES = {"classsum": _lib.DRAM_HEAT_CLASSSUM, "plain": _lib.DRAM_HEAT_PLAIN}
+
+
+def _heat_dense(dense: Tensor, name: str):
+    """One head's dense maps [B,C,d,h,w] float32, e.g. a channel view of the engine's one tensor: only the innermost
+    three dimensions must be contiguous -> (B, C, d, h, w, batch stride, channel stride) in elements."""
+    if not isinstance(dense, Tensor) or dense.dim() != 5 or min(dense.shape) < 1:
+        raise ValueError(f"{name}: dense must be a non-empty [B,C,d,h,w] tensor")
+    B, C, d, h, w = (int(s) for s in dense.shape)
+    if w % 4:
+        raise ValueError(f"{name}: the dense grid's w must be a multiple of 4 (the scan's W of 8), got {w}")
+    if 8 * d * h * w >= 2 ** 31:
+        raise ValueError(f"{name}: output grids of 2^31 voxels or more are not supported")
+    try:
+        _req(dense[0, 0], f"{name}: dense[b, c]")           # device, dtype, contiguous [d,h,w]
+    except ValueError:
+        raise ValueError(f"{name}: the innermost three dimensions of dense must be contiguous") from None
+    sb, sc = (int(dense.stride(0)) if B > 1 else 0), (int(dense.stride(1)) if C > 1 else 0)
+    if sb < 0 or sc < 0 or sb % 4 or sc % 4 or dense.data_ptr() % 16:
+        raise ValueError(f"{name}: dense must be 16-byte aligned with non-negative batch / channel strides that are "
+                         "multiples of 4 elements")
+    return B, C, d, h, w, sb, sc
+
+
+def heat_peak(dense: Tensor) -> Tensor:
+    """peak [B] float32 = max over the whole x2 trilinear up-sampled volume (align_corners=False) of
+    sum_{c>=1} relu(up_c), the normaliser of the classification maps (reference models.py:217-222), taken BEFORE the
+    lung mask.  dense [B,C>=2,d,h,w] float32, batch / channel strides free (see heat_volume).  One reduction pass
+    (per-block maxima) and an amax over [B,nblk] as glue; the up-sampled channels are never stored."""
+    B, C, d, h, w, sb, sc = _heat_dense(dense, "heat_peak")
+    if C < 2:
+        raise ValueError("heat_peak: the class sum runs over the channels 1..C-1: C >= 2")
+    nblk = _L().dram_heat_nblk(8 * d * h * w)
+    partial = torch.empty((B, nblk), device=dense.device, dtype=torch.float32)
+    _chk(_L().dram_heat_peak(_p(dense), sb, sc, C, _p(partial), B, d, h, w, 2 * d, 2 * h, 2 * w, _stream()),
+         "dram_heat_peak")
+    return partial.amax(1)
+
+
+def heat_volume(dense: Tensor, lung: Tensor, mode: str, peak: Optional[Tensor] = None, zsel=None,
+                want_f32: bool = False, want_u8: bool = True):
+    """The heat volume the reference's _draw_predictions draws (models.py:201-229 / :464-488), fused into one pass:
+    mode "classsum": sum_{c>=1} relu(up_c) / (peak + 1e-7) * lung, `peak` from heat_peak; "plain" (C == 1): up_0 * lung;
+    up = F.interpolate(dense, size=(2d,2h,2w), mode='trilinear'), recomputed from dense and never stored.
+
+    dense [B,C,d,h,w] float32 with free batch / channel strides (`dense_all[:, :n0]` works without a copy);
+    lung [B,2d,2h,2w] bool / uint8, non-zero = lung.  zsel: [B,nz] output-grid z indices in [0, 2d) (per sample,
+    repeats allowed; a host sequence, or a tensor -- a device tensor is read back for the range check): the result is
+    [B,nz,2h,2w], those slices of the full [B,2d,2h,2w] result bit for bit.
+    -> (f32 or None, u8 or None): v unclamped, and trunc(255 * clamp(v, 0, 1)).  Every check runs before any launch."""
+    if mode not in HEAT_MODES:
+        raise ValueError(f"heat_volume: unknown mode {mode!r} (one of {sorted(HEAT_MODES)})")
+    if not (want_f32 or want_u8):
+        raise ValueError("heat_volume: nothing to write (want_f32 and want_u8 are both off)")
+    B, C, d, h, w, sb, sc = _heat_dense(dense, "heat_volume")
+    D, H, W = 2 * d, 2 * h, 2 * w
+    if mode == "classsum":
+        if C < 2:
+            raise ValueError("heat_volume: 'classsum' runs over the channels 1..C-1: C >= 2")
+        if peak is None:
+            raise ValueError("heat_volume: 'classsum' needs the peak (heat_peak(dense))")
+        _req(peak, "peak", shape=(B,))
+    elif C != 1:
+        raise ValueError(f"heat_volume: 'plain' takes one channel, got {C}")
+    if not isinstance(lung, Tensor) or lung.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"heat_volume: lung must be bool or uint8, got {getattr(lung, 'dtype', type(lung))}")
+    if tuple(lung.shape) != (B, D, H, W):
+        raise ValueError(f"heat_volume: lung must be {(B, D, H, W)} (twice the dense grid), got {tuple(lung.shape)}")
+    if lung.dtype == torch.bool:
+        lung = lung.contiguous().view(torch.uint8)
+    _req(lung, "lung", torch.uint8)
+    if lung.data_ptr() % 8:                     # the kernel reads 8 mask bytes per lane
+        lung = lung.clone()
+    zs, nz = None, 0
+    if zsel is not None:
+        zh = torch.as_tensor(zsel).cpu()
+        if zh.dim() != 2 or zh.shape[0] != B or zh.shape[1] < 1 or zh.is_floating_point():
+            raise ValueError(f"heat_volume: zsel must be [B={B}, nz >= 1] integers, got {tuple(zh.shape)} {zh.dtype}")
+        if int(zh.min()) < 0 or int(zh.max()) >= D:
+            raise ValueError(f"heat_volume: zsel entries must lie in [0, {D})")
+        nz = int(zh.shape[1])
+        if nz * H * W >= 2 ** 31:
+            raise ValueError("heat_volume: zsel selects 2^31 voxels or more")
+        zs = zh.to(torch.int32).contiguous().to(dense.device)
+    shape = (B, nz if zs is not None else D, H, W)
+    f32 = torch.empty(shape, device=dense.device, dtype=torch.float32) if want_f32 else None
+    u8 = torch.empty(shape, device=dense.device, dtype=torch.uint8) if want_u8 else None
+    _chk(_L().dram_heat_volume(_p(dense), sb, sc, C, _p(lung), _p(peak), _p(zs), nz, _p(f32), _p(u8), HEAT_MODES[mode],
+                               B, d, h, w, D, H, W, _stream()), "dram_heat_volume")
+    return f32, u8
+
+
 def segloss_fwd(cle: Tensor, pse: Tensor, lungs: Tensor, ems: Tensor, binary: Tensor,
                 smoothness: float = 0.85) -> Tensor:
     """cle/pse [B,D,H,W]; lungs/ems [B,Dl,Hl,Wl]; binary [B] -> partial [nblk,6].  smoothness: the in-mask

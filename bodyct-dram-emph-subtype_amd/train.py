@@ -66,6 +66,9 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--gradient_clip_val", default=None, type=float)
     p.add_argument("--gradient_clip_algorithm", default="norm", type=str, choices=("norm", "value"))
     p.add_argument("--accumulate_grad_batches", default=1, type=int)
+    # activation-map sheets of the first N validation / test batches (the reference's _draw_predictions, which
+    # hard-codes N = 50), written on rank 0 under <model_path>/debug_input_data/<epoch>/<stage>/
+    p.add_argument("--draw_predictions", default=0, type=int)
     return p
 
 
@@ -212,6 +215,7 @@ def run_training_job(argv=None):
         # Lightning's fit loop: validation epoch, then the epoch-end hooks (gather + de-dup + class-weight update,
         # models.py:287-317 / :367-379), then the scheduler and ModelCheckpoint
         module.eval()
+        module.epoch_number = epoch                # the folder draw_predictions writes to (models.py:194-197)
         val_outputs = [module.validation_step(b, i) for i, b in enumerate(val_data.epoch(epoch))]
         ev = module.validation_epoch_end(val_outputs)
         et = module.training_epoch_end(step_outputs)

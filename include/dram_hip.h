@@ -509,6 +509,33 @@ int dram_upproject_nblk(long long voxels_per_sample);
 int dram_upproject(const float* dense, const float* ess, float* out, float* partial, int B, int D, int H,
                    int W, int Do, int Ho, int Wo, dram_stream_t stream);
 
+/* Validation / test activation-map volumes (_draw_predictions, models.py:192-234 / :455-493), csrc/heat.hip.
+ *   dense: head outputs of one head, C channels [d,h,w] (innermost three dimensions contiguous) at
+ *     dense + b * stride_b + c * stride_c (strides in ELEMENTS, multiples of 4; dense 16-byte aligned; w % 4 == 0),
+ *     so both heads read the engine's one [B,n0+n1,d,h,w] tensor through its channel views without a copy.
+ *   up_c = F.interpolate(dense[b,c], size=(D,H,W)=(2d,2h,2w), mode='trilinear'), align_corners=False: source
+ *     coordinate max(k/2 - 0.25, 0), weights {0.25, 0.75} ({1, 0} at k = 0), far tap clamped to n - 1.  The
+ *     up-sampled channels are never stored; both passes recompute them from dense.
+ *   DRAM_HEAT_CLASSSUM (C >= 2): dp = sum_{c>=1} max(up_c, 0);  v = dp / (peak[b] + 1e-7f) * lung
+ *   DRAM_HEAT_PLAIN    (C == 1): v = up_0 * lung
+ *   lung [B][D][H][W] bytes (bool / uint8), non-zero = 1.0f, 8-byte aligned.
+ * dram_heat_peak: partial [B][nblk], nblk = dram_heat_nblk(D*H*W): per-block maxima of dp over the WHOLE volume, before
+ *   the lung mask; the caller folds them (max over nblk) into peak [B].
+ * dram_heat_volume: out_f32 = v (unclamped) and / or out_u8 = trunc(255 * clamp(v, 0, 1)), either may be NULL, each
+ *   [B][D][H][W] -- or, with zsel [B][nz] int32 (output-grid z indices in [0, D), per sample, repeats allowed; the
+ *   caller checks the range), [B][nz][H][W]: those slices of the full result, bit for bit.  nz is ignored without zsel.
+ *   Every output element is written.  peak is read in CLASSSUM only.
+ * No atomics, fixed order: bit-identical from call to call.  D*H*W >= 2^31: DRAM_ERR_UNSUPPORTED; an output grid that
+ * is not exactly twice the dense grid, a channel count the mode does not take, zsel with nz <= 0: DRAM_ERR_BAD_ARG. */
+#define DRAM_HEAT_CLASSSUM 0
+#define DRAM_HEAT_PLAIN 1
+int dram_heat_nblk(long long voxels_per_sample);
+int dram_heat_peak(const float* dense, long long stride_b, long long stride_c, int C, float* partial, int B, int d,
+                   int h, int w, int D, int H, int W, dram_stream_t stream);
+int dram_heat_volume(const float* dense, long long stride_b, long long stride_c, int C, const uint8_t* lung,
+                     const float* peak, const int* zsel, int nz, float* out_f32, uint8_t* out_u8, int mode, int B,
+                     int d, int h, int w, int D, int H, int W, dram_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Multi-tensor optimizers -- torch.optim.Adam at models.py:385-387 / :689-691 and the
  * SGD arguments of train.py:25,27.  table: device array of DramTensorRef[ntensors];
