@@ -566,10 +566,18 @@ class ScanRegLightningModule(_ScanModule):
 
     def predict_step(self, batch, batch_idx: int, dataloader_idx: int = 0):
         """models.py:430-450: eval forward, dRAM up-projection to the scan grid x ess mask,
-        percentages normalised by lungs.sum() over the WHOLE batch (:440-441)."""
+        percentages normalised by lungs.sum() over the WHOLE batch (:440-441).
+
+        A batch that holds 'lobe_labels' ([B,D,H,W] uint8 on the network grid, ``transforms.prepare_labels``) takes the
+        fused tail (``ops.upproject_regions``: both heads and a per-region table in one pass) and returns in addition
+        'region_table' [B, n+1, 4] float64 (rows 0..n: sum cle, sum pse, #ess, #voxels; row 0 = label 0 and labels above
+        n = ``args.n_regions``, default 5), 'cle_region_percentages' / 'pse_region_percentages' [B, n] (sum / #voxels of
+        that sample's region, NaN for an absent region), 'region_voxels' [B, n] and 'region_ess_fraction' [B, n]."""
         with torch.no_grad():
             scans = batch["image"].unsqueeze(1)
             lungs = batch["lung_mask"].unsqueeze(1).float()
+            if batch.get("lobe_labels") is not None:
+                return self._predict_regions(batch, scans, lungs)
             ess = batch["ess_mask"].unsqueeze(1).float()
             dense_outs, _ = self.forward(scans, lungs)
             B = scans.shape[0]
@@ -584,6 +592,34 @@ class ScanRegLightningModule(_ScanModule):
             res.update(crop_slices=batch.get("crop_slice"), original_size=batch.get("original_size"),
                        uids=batch.get("uid"))
             return res
+
+    def _predict_regions(self, batch, scans, lungs):
+        """predict_step's tail for a batch with 'lobe_labels': one fused pass instead of the two up-projections."""
+        def as_bytes(m, name):
+            if m.dtype not in (torch.bool, torch.uint8):
+                if name == "lobe_labels":
+                    raise TypeError(f"predict_step: 'lobe_labels' must be uint8 (transforms.prepare_labels), got {m.dtype}")
+                m = m != 0
+            return m.contiguous().view(torch.uint8) if m.dtype == torch.bool else m.contiguous()
+
+        dense_outs, _ = self.forward(scans, lungs)
+        B = scans.shape[0]
+        size = tuple(scans.shape[-3:])
+        n = int(getattr(self.args, "n_regions", 5))
+        heads = [d.reshape(B, *d.shape[-3:]) for d in dense_outs[:2]]          # channel views: no copy
+        if B > 1 and heads[0].stride(0) != heads[1].stride(0):
+            heads = [h.contiguous() for h in heads]
+        up_c, up_p, table = ops.upproject_regions(heads[0], heads[1], as_bytes(batch["ess_mask"], "ess_mask").reshape(B, *size),
+                                                  as_bytes(batch["lobe_labels"], "lobe_labels").reshape(B, *size), size, n)
+        lung_sum = lungs.sum()
+        vox = table[:, 1:, 3]
+        res = {"cle_dense_outs": up_c.unsqueeze(1), "cle_precentages": (table[:, :, 0].sum(1) / lung_sum).float(),
+               "pse_dense_outs": up_p.unsqueeze(1), "pse_precentages": (table[:, :, 1].sum(1) / lung_sum).float(),
+               "region_table": table, "cle_region_percentages": table[:, 1:, 0] / vox,
+               "pse_region_percentages": table[:, 1:, 1] / vox, "region_voxels": vox.round().long(),
+               "region_ess_fraction": table[:, 1:, 2] / vox}
+        res.update(crop_slices=batch.get("crop_slice"), original_size=batch.get("original_size"), uids=batch.get("uid"))
+        return res
 
 
 def make_args(model_arch: str, lr: float = 1e-4, **kw) -> SimpleNamespace:

@@ -1300,6 +1300,53 @@ def upproject(dense: Tensor, ess: Tensor, size):
     return out, partial
 
 
+def upproject_regions(cle: Tensor, pse: Tensor, ess_u8: Tensor, labels_u8: Tensor, size, n_regions: int = 5,
+                      want_volumes: bool = True):
+    """Both heads' ``upproject`` and the per-region table in one pass (csrc/regions.hip).
+
+    cle, pse [B,D,H,W] float32: each sample contiguous, ONE batch stride for both (two channel views of the engine's one
+    dense tensor work without a copy); ess_u8, labels_u8 [B,Do,Ho,Wo] uint8 (bool is viewed as bytes), ess non-zero =
+    1.0.  -> (up_cle, up_pse, table): the volumes [B,Do,Ho,Wo], bit for bit ``upproject(head, ess.float(), size)[0]``
+    (None, None when ``want_volumes`` is off), and table [B, n_regions + 1, 4] float64, row r = (sum up_cle, sum up_pse,
+    #(ess != 0), #voxels) over labels == r; row 0 also takes every label above n_regions.  Deterministic; every check
+    runs before any launch."""
+    n = int(n_regions)
+    if not 1 <= n <= 15:
+        raise ValueError(f"upproject_regions: n_regions must be 1..15, got {n_regions}")
+    for t, name in ((cle, "cle"), (pse, "pse")):
+        if not isinstance(t, Tensor) or t.dim() != 4 or min(t.shape) < 1:
+            raise ValueError(f"upproject_regions: {name} must be a non-empty [B,D,H,W] tensor")
+        try:
+            _req(t[0], f"upproject_regions: {name}[b]")          # device, dtype, contiguous [D,H,W]
+        except ValueError:
+            raise ValueError(f"upproject_regions: the innermost three dimensions of {name} must be contiguous") from None
+    B, D, H, W = (int(s) for s in cle.shape)
+    if tuple(pse.shape) != (B, D, H, W):
+        raise ValueError(f"upproject_regions: pse {tuple(pse.shape)} must have cle's shape {(B, D, H, W)}")
+    sb = int(cle.stride(0)) if B > 1 else D * H * W
+    if B > 1 and (int(pse.stride(0)) != sb or sb < D * H * W):
+        raise ValueError("upproject_regions: cle and pse must share one batch stride >= D*H*W "
+                         f"(got {cle.stride(0)} and {pse.stride(0)})")
+    Do, Ho, Wo = (int(v) for v in size)
+    if min(Do, Ho, Wo) < 1 or Do * Ho * Wo >= 2 ** 31 or D * H * W >= 2 ** 31:
+        raise ValueError(f"upproject_regions: size {(Do, Ho, Wo)} must be positive and below 2^31 voxels")
+    masks = []
+    for t, name in ((ess_u8, "ess_u8"), (labels_u8, "labels_u8")):
+        if isinstance(t, Tensor) and t.dtype == torch.bool:
+            t = t.contiguous().view(torch.uint8)
+        masks.append(_req(t, f"upproject_regions: {name}", torch.uint8, shape=(B, Do, Ho, Wo)))
+    ess_u8, labels_u8 = masks
+    dev = cle.device
+    nblk = _L().dram_region_nblk(Do * Ho * Wo)
+    up_c = torch.empty((B, Do, Ho, Wo), device=dev, dtype=torch.float32) if want_volumes else None
+    up_p = torch.empty((B, Do, Ho, Wo), device=dev, dtype=torch.float32) if want_volumes else None
+    partial = torch.empty((B, nblk, n + 1, 4), device=dev, dtype=torch.float32)
+    table = torch.empty((B, n + 1, 4), device=dev, dtype=torch.float64)
+    _chk(_L().dram_upproject_regions(_p(cle), _p(pse), sb, _p(ess_u8), _p(labels_u8), _p(up_c), _p(up_p), _p(partial),
+                                     _p(table), B, D, H, W, Do, Ho, Wo, n, _stream()), "dram_upproject_regions")
+    return up_c, up_p, table
+
+
 # --------------------------------------------------------------------------- heads / losses
 def head_fwd(x: Tensor, w: Tensor, bias: Tensor, lungs: Optional[Tensor], sigmoid: bool):
     """x [B,D,H,W,32] (float32 or bfloat16); w [NO,32]; lungs None or [B,Dl,Hl,Wl] full-res mask.  The dense maps

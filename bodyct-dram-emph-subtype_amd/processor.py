@@ -51,9 +51,42 @@ def resample_paste(dense: torch.Tensor, crop_slice, original_size: Sequence[int]
     return of, ob
 
 
-def build_outputs(predictions: List[dict], want_u8: bool = True) -> List[dict]:
+REGION_KEYS = ("cle_lesion_percentage_per_region", "cle_severity_score_per_region", "pse_lesion_percentage_per_region",
+               "pse_severity_score_per_region", "region_voxels", "region_ess_fraction")
+
+
+def region_metrics(table_row, names=None) -> dict:
+    """One sample's region table [n+1, 4] (predict_step's 'region_table'[b]: rows 0..n of sum cle, sum pse, #ess,
+    #voxels) -> the regional entries of the metrics dict, in the formats of the per-lung ones: per region the lesion
+    percentage sum / #voxels ("{:.3f}"), its severity score (``ratio_to_label`` on the same bands, "{:d}"), the voxel
+    count ("{:d}") and the share of the region below the ess threshold ("{:.3f}").  Each value is a dict keyed by
+    ``names[label]`` (a mapping or a sequence indexed by the label) or else by the label as a string, the form json
+    gives it.  A region without voxels has None (json null) for everything but its count.  Pure host code."""
+    rows = table_row.tolist() if torch.is_tensor(table_row) else [list(r) for r in table_row]
+    if len(rows) < 2 or any(len(r) != 4 for r in rows):
+        raise ValueError("region_metrics: table_row must be [n_regions + 1, 4]")
+    out = {k: {} for k in REGION_KEYS}
+    for label in range(1, len(rows)):
+        try:
+            key = str(names[label]) if names is not None else str(label)
+        except (KeyError, IndexError):
+            key = str(label)
+        s_cle, s_pse, n_ess, n_vox = (float(v) for v in rows[label])
+        present = n_vox > 0
+        for head, s, rmap in (("cle", s_cle, CLE_RATIO_MAP), ("pse", s_pse, PSE_RATIO_MAP)):
+            pct = s / n_vox if present else None
+            out[f"{head}_lesion_percentage_per_region"][key] = "{:.3f}".format(pct) if present else None
+            out[f"{head}_severity_score_per_region"][key] = "{:d}".format(ratio_to_label(pct, rmap)) if present else None
+        out["region_voxels"][key] = "{:d}".format(int(round(n_vox)))
+        out["region_ess_fraction"][key] = "{:.3f}".format(n_ess / n_vox) if present else None
+    return out
+
+
+def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=None) -> List[dict]:
     """processor.py:102-145 for a list of predict_step outputs: per scan the pasted CLE / PSE volumes (uint8 like
-    the written .mha, and/or float) and the metrics entry of the results json."""
+    the written .mha, and/or float) and the metrics entry of the results json.  A prediction that carries a
+    'region_table' adds ``region_metrics`` to its metrics, and a line in error_messages when row 0 of the table holds
+    ess voxels: ess lies inside the lung, so those are lung voxels whose label is outside 1..n_regions."""
     results = []
     for out in predictions:
         B = out["cle_dense_outs"].shape[0]
@@ -70,27 +103,38 @@ def build_outputs(predictions: List[dict], want_u8: bool = True) -> List[dict]:
                        "cle_lesion_percentage_per_lung": "{:.3f}".format(cle_p),
                        "pse_severity_score": "{:d}".format(ratio_to_label(pse_p, PSE_RATIO_MAP)),
                        "pse_lesion_percentage_per_lung": "{:.3f}".format(pse_p)}
+            errors = []
+            if out.get("region_table") is not None:
+                row = out["region_table"][b].cpu()
+                metrics.update(region_metrics(row, region_names))
+                if float(row[0, 2]) > 0:
+                    errors.append("{:d} ess voxels carry a lobe label outside 1..{:d}: they are in no region".format(
+                        int(round(float(row[0, 2]))), row.shape[0] - 1))
             uid = out["uids"][b] if out.get("uids") is not None else None
-            results.append({"entity": uid, "metrics": metrics, "error_messages": [], "full_cle": vols["cle"],
+            results.append({"entity": uid, "metrics": metrics, "error_messages": errors, "full_cle": vols["cle"],
                             "full_pse": vols["pse"]})
     return results
 
 
 def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[float], target_size: Sequence[int],
-                 uid=None, want_u8: bool = True, **prepare_kw) -> dict:
+                 uid=None, want_u8: bool = True, regions: bool = False, region_names=None, **prepare_kw) -> dict:
     """One scan + its lobe segmentation -> its entry of ``build_outputs``: ``transforms.prepare_case`` (dataset.py:57-92)
     -> ``transforms.prepare_sample(target_size)`` -> a batch of one -> ``module.predict_step`` -> ``build_outputs``.
-    The composition only; `prepare_kw` goes to ``prepare_case`` (crop_border, dilate_iterations, ...)."""
-    case = transforms.prepare_case(scan, lobes, spacing, uid=uid, **prepare_kw)
+    The composition only; `prepare_kw` goes to ``prepare_case`` (crop_border, dilate_iterations, ...).  ``regions``:
+    the lobe labels travel along (``prepare_case(want_lobes=True)``) and the entry carries the per-lobe metrics of
+    ``region_metrics``, keyed through ``region_names``."""
+    case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=bool(regions), **prepare_kw)
     sample = transforms.prepare_sample(case, target_size)
-    batch = {k: sample[k].unsqueeze(0) for k in ("image", "lung_mask", "ess_mask", "crop_slice", "original_size")}
+    keys = ("image", "lung_mask", "ess_mask", "crop_slice", "original_size") + (("lobe_labels",) if regions else ())
+    batch = {k: sample[k].unsqueeze(0) for k in keys}
     batch["uid"] = [uid]
-    return build_outputs([module.predict_step(batch, 0)], want_u8=want_u8)[0]
+    return build_outputs([module.predict_step(batch, 0)], want_u8=want_u8, region_names=region_names)[0]
 
 
 def write_reports(results: List[dict], centrilobular_json: Optional[str] = None, paraseptal_json: Optional[str] = None,
-                  output_json: Optional[str] = None):
-    """processor.py:160-177: the two single-scan score files and the results list."""
+                  output_json: Optional[str] = None, regions_json: Optional[str] = None):
+    """processor.py:160-177: the two single-scan score files and the results list; ``regions_json``: the regional
+    entries (``REGION_KEYS``) of the first result, which must carry them."""
     m = results[0]["metrics"]
     if centrilobular_json:
         with open(centrilobular_json, "w") as f:
@@ -103,3 +147,8 @@ def write_reports(results: List[dict], centrilobular_json: Optional[str] = None,
     if output_json:
         with open(output_json, "w") as f:
             f.write(json.dumps([{k: r[k] for k in ("entity", "metrics", "error_messages")} for r in results]))
+    if regions_json:
+        if any(k not in m for k in REGION_KEYS):
+            raise ValueError("write_reports: regions_json needs a result with regional metrics (predict_case(regions=True))")
+        with open(regions_json, "w") as f:
+            f.write(json.dumps({k: m[k] for k in REGION_KEYS}))

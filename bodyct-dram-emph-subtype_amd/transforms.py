@@ -71,14 +71,42 @@ def prepare_mask(mask: torch.Tensor, target_size: Sequence[int]) -> torch.Tensor
     return out.to(dtype)
 
 
+def prepare_labels(labels: torch.Tensor, target_size: Sequence[int]) -> torch.Tensor:
+    """labels [D,H,W] uint8 / int16 / bool (a view with unit x stride is read in place, e.g. the lung crop of the lobe
+    volume) -> uint8 [Do,Ho,Wo]: ``prepare_mask``'s nearest rule, values clamped to 0..255.  The source is neither
+    copied nor converted to float; ``prepare_labels(l) > 0`` equals ``prepare_mask(l > 0)`` voxel for voxel."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or min(labels.shape) < 1:
+        raise ValueError("prepare_labels: labels must be a non-empty [D,H,W] tensor")
+    if labels.dtype == torch.bool:
+        labels = labels.view(torch.uint8)
+    if labels.dtype not in (torch.uint8, torch.int16):
+        raise TypeError(f"prepare_labels: expected uint8, int16 or bool labels, got {labels.dtype}")
+    D, H, W = (int(v) for v in labels.shape)
+    if (W > 1 and labels.stride(2) != 1) or min(labels.stride()) < 0:
+        labels = labels.contiguous()
+    _req(labels[0, 0], "labels", labels.dtype)                   # device; a row is contiguous
+    Do, Ho, Wo = (int(v) for v in target_size)
+    if min(Do, Ho, Wo) < 1:
+        raise ValueError(f"prepare_labels: target_size {(Do, Ho, Wo)} must be positive")
+    zidx = depth_indices(D, Do, labels.device)
+    out = torch.empty((Do, Ho, Wo), device=labels.device, dtype=torch.uint8)
+    _chk(_L().dram_prep_labels(_p(labels), 2 if labels.dtype == torch.int16 else 1, int(labels.stride(0)),
+                               int(labels.stride(1)), _p(zidx), _p(out), D, H, W, Do, Ho, Wo, _stream()),
+         "dram_prep_labels")
+    return out
+
+
 def prepare_sample(sample: Dict[str, torch.Tensor], target_size: Sequence[int]) -> Dict[str, torch.Tensor]:
-    """Dict transform with the reference's keys: 'image' + '*_mask' entries (base.py dict transforms)."""
+    """Dict transform with the reference's keys: 'image' + '*_mask' entries (base.py dict transforms); 'lobe_labels'
+    (``prepare_case(want_lobes=True)``) goes through ``prepare_labels``."""
     out = dict(sample)
     for k, v in sample.items():
         if k == "image":
             out[k] = prepare_image(v, target_size)
         elif k.endswith("_mask"):
             out[k] = prepare_mask(v, target_size)
+        elif k == "lobe_labels":
+            out[k] = prepare_labels(v, target_size)
     return out
 
 
@@ -98,7 +126,7 @@ def _lobes_operand(lobes: torch.Tensor):
 
 def prepare_case(scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[float], crop_border: float = 5,
                  dilate_iterations: int = 2, fill_value: int = -2048, ess_threshold: int = -910,
-                 want_original: bool = False, uid=None) -> Dict[str, object]:
+                 want_original: bool = False, uid=None, want_lobes: bool = False) -> Dict[str, object]:
     """The reference's ``SubtypingInference.get_data`` (dataset.py:57-92) with ``utils.find_crops`` (utils.py:53-63) on
     the device: lung = lobes > 0; the scan outside ``dilate_iterations`` dilations of the lung (full 3x3x3 structure)
     is set to ``fill_value``; scan, lung and (``want_original``) the untouched scan are cropped to the lung's bounding
@@ -109,7 +137,10 @@ def prepare_case(scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[floa
     returns it.  A scan that is not int16 is converted with ``.to(torch.int16)`` first (the reference's
     ``astype(np.int16)``) and the threshold applies to the converted values.  Returns the reference's keys: 'image'
     int16, 'lung_mask' / 'ess_mask' bool, 'original_image' int16 (only when asked), 'crop_slice' int64 [3,2] and
-    'original_size' int64 [3] (host tensors), 'uid'.  The dict feeds ``prepare_sample`` unchanged.
+    'original_size' int64 [3] (host tensors), 'uid'.  The dict feeds ``prepare_sample`` unchanged.  ``want_lobes`` adds
+    'lobe_labels': the crop of the lobe volume itself, a VIEW (uint8 / int16 / bool lobes are not copied; any other
+    integer type is clamped to 0..255 as uint8 first, floating-point lobes are refused), which ``prepare_sample`` resizes
+    with ``prepare_labels`` -- so that ``lobe_labels > 0`` is the resized 'lung_mask' voxel for voxel.
 
     The bounding box is read back to the host once per case, because the sizes of the outputs depend on it: the call
     synchronises with the device and cannot be captured into a hipGraph.  Raises IndexError for an empty lung (as
@@ -129,6 +160,10 @@ def prepare_case(scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[floa
         raise ValueError("prepare_case: spacing must have three entries (z, y, x)")
     scan = scan.to(torch.int16).contiguous()
     _req(scan, "scan", torch.int16)
+    if want_lobes and lobes.dtype not in (torch.bool, torch.uint8, torch.int16):
+        if lobes.is_floating_point():
+            raise TypeError("prepare_case: want_lobes needs integer lobe labels")
+        lobes = lobes.clamp(0, 255).to(torch.uint8)
     lobes, code = _lobes_operand(lobes)
     _req(lobes, "lobes", lobes.dtype)
     D, H, W = (int(v) for v in scan.shape)
@@ -156,6 +191,8 @@ def prepare_case(scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[floa
            "uid": uid}
     if want_original:
         out["original_image"] = orig
+    if want_lobes:
+        out["lobe_labels"] = lobes[z0:z1, y0:y1, x0:x1]
     return out
 
 

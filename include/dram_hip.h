@@ -509,6 +509,28 @@ int dram_upproject_nblk(long long voxels_per_sample);
 int dram_upproject(const float* dense, const float* ess, float* out, float* partial, int B, int D, int H,
                    int W, int Do, int Ho, int Wo, dram_stream_t stream);
 
+/* Predict-time up-projection of BOTH heads with a per-region table (csrc/regions.hip; the reference has no regional
+ * code: with every lung label <= n_regions the table reduces to its per-lung number, models.py:438-441).
+ *   cle, pse: the two heads' dense maps [D,H,W] of sample b at cle / pse + b * dense_batch_stride (elements): two
+ *     channel views of one tensor need no copy.  ess, labels [B][Do][Ho][Wo] bytes (ess: non-zero = 1.0f).
+ *   out_cle, out_pse [B][Do][Ho][Wo] = trilinear(dense -> Do,Ho,Wo, align_corners) * ess, bit for bit what
+ *     dram_upproject stores; both NULL: the table only.
+ *   table [B][n_regions + 1][4] double, row r = { sum out_cle, sum out_pse, #(ess != 0), #voxels } over the voxels with
+ *     labels == r; row 0 also collects every label above n_regions.  partial [B][nblk][n_regions + 1][4] float scratch,
+ *     nblk = dram_region_nblk(Do*Ho*Wo) (every row is written: no memset); a second launch folds it per sample in index
+ *     order in double.  No atomics: bit-identical from call to call.  The counts are exact.
+ * n_regions 1..15, dense_batch_stride >= D*H*W, sizes >= 1, exactly one of out_cle / out_pse NULL: DRAM_ERR_BAD_ARG;
+ * Do*Ho*Wo or D*H*W >= 2^31, B > 65535: DRAM_ERR_UNSUPPORTED.
+ * dram_prep_labels: out [Do,Ho,Wo] bytes = clamp(labels[zidx[zo]][ys][xs], 0, 255), ys / xs = min(floor(dst * in/out),
+ *   in - 1) as dram_prep_mask; labels of label_dtype 1 (uint8) or 2 (int16) is a [D,H,W] view read through its element
+ *   strides (x stride 1, strides >= 0), e.g. the lung crop of the lobe volume: never copied or converted. */
+int dram_region_nblk(long long voxels_per_sample);
+int dram_upproject_regions(const float* cle, const float* pse, long long dense_batch_stride, const uint8_t* ess,
+                           const uint8_t* labels, float* out_cle, float* out_pse, float* partial, double* table, int B,
+                           int D, int H, int W, int Do, int Ho, int Wo, int n_regions, dram_stream_t stream);
+int dram_prep_labels(const void* labels, int label_dtype, long long stride_z, long long stride_y, const int* zidx,
+                     uint8_t* out, int D, int H, int W, int Do, int Ho, int Wo, dram_stream_t stream);
+
 /* Validation / test activation-map volumes (_draw_predictions, models.py:192-234 / :455-493), csrc/heat.hip.
  *   dense: head outputs of one head, C channels [d,h,w] (innermost three dimensions contiguous) at
  *     dense + b * stride_b + c * stride_c (strides in ELEMENTS, multiples of 4; dense 16-byte aligned; w % 4 == 0),

@@ -24,7 +24,7 @@ FAMILIES = [("conv3_bf16", "conv_bf16"), ("gemm1_bf16", "conv_bf16"), ("wgrad3",
             ("stem_", "stem"), ("bn_", "bn_elementwise"), ("colreduce", "bn_elementwise"),
             ("reduce_partials", "bn_elementwise"), ("fold_partials", "bn_elementwise"), ("add_kernel", "bn_elementwise"),
             ("upmix_axis", "pool_up"), ("upmix_split", "weight_pack"), ("upmix_merge", "weight_pack"), ("maxpool", "pool_up"),
-            ("upcat", "pool_up"), ("upproject", "pool_up"), ("head_", "head_loss"), ("segloss", "head_loss"),
+            ("upcat", "pool_up"), ("upproject", "pool_up"), ("region_fold", "pool_up"), ("head_", "head_loss"), ("segloss", "head_loss"),
             ("adam_multi", "optim"), ("sgd_multi", "optim"), ("window_stats", "prep"), ("prep_", "prep")]
 
 
