@@ -1347,6 +1347,49 @@ def upproject_regions(cle: Tensor, pse: Tensor, ess_u8: Tensor, labels_u8: Tenso
     return up_c, up_p, table
 
 
+def lobe_histogram(image: Tensor, labels: Tensor, n_regions: int = 5, hu_lo: int = -1024, nbins: int = 1024):
+    """Per-region 1-HU histogram of a scan in one pass (csrc/densito.hip).
+
+    image [D,H,W] int16 HU, contiguous (``prepare_case``'s 'image'); labels [D,H,W] uint8 / int16 / bool, read in place
+    through their z / y strides when the x stride is 1 (``prepare_case``'s 'lobe_labels' view; any other view is made
+    contiguous first).  -> (hist, sums): hist [n_regions + 1, nbins] int64, voxels per row and bin
+    ``clamp(hu, hu_lo, hu_lo + nbins - 1) - hu_lo`` (the end bins collect the tails); sums [n_regions + 1, 2] int64 =
+    (voxel count, sum of the raw HU values).  Label r in 1..n_regions -> row r, a label above n_regions -> row 0, a
+    label <= 0 is counted nowhere, so the rows add up to ``labels > 0``.  Supported: nbins a multiple of 64 in 64..2048,
+    (n_regions + 1) * nbins <= 32768, hu_lo .. hu_lo + nbins - 1 inside int16, fewer than 2^31 voxels.  Integer counts:
+    bit-identical from call to call; never synchronises; every check runs before any launch."""
+    n, lo, nb = int(n_regions), int(hu_lo), int(nbins)
+    if not 1 <= n <= 15:
+        raise ValueError(f"lobe_histogram: n_regions must be 1..15, got {n_regions}")
+    for t, name in ((image, "image"), (labels, "labels")):
+        if not isinstance(t, Tensor) or t.dim() != 3 or min(t.shape) < 1:
+            raise ValueError(f"lobe_histogram: {name} must be a non-empty [D,H,W] tensor")
+    if labels.dtype == torch.bool:
+        labels = labels.view(torch.uint8)
+    if labels.dtype not in (torch.uint8, torch.int16):
+        raise TypeError(f"lobe_histogram: expected uint8, int16 or bool labels, got {labels.dtype}")
+    if tuple(labels.shape) != tuple(image.shape):
+        raise ValueError(f"lobe_histogram: labels {tuple(labels.shape)} must have the image's shape {tuple(image.shape)}")
+    D, H, W = (int(v) for v in image.shape)
+    if D * H * W >= 2 ** 31:
+        raise ValueError("lobe_histogram: volumes of 2^31 voxels or more are not supported")
+    if (W > 1 and labels.stride(2) != 1) or min(labels.stride()) < 0:
+        labels = labels.contiguous()
+    dev = image.device
+    with launch_scope(dev):
+        _req(image, "lobe_histogram: image", torch.int16)
+        _req(labels[0, 0], "lobe_histogram: labels", labels.dtype)       # device; a row is contiguous
+        nblk = _L().dram_lobe_hist_nblk(D * H * W)
+        part_hist = torch.empty((nblk, n + 1, nb), device=dev, dtype=torch.int32)
+        part_sums = torch.empty((nblk, n + 1, 2), device=dev, dtype=torch.int64)
+        hist = torch.empty((n + 1, nb), device=dev, dtype=torch.int64)
+        sums = torch.empty((n + 1, 2), device=dev, dtype=torch.int64)
+        _chk(_L().dram_lobe_hist(_p(image), _p(labels), 2 if labels.dtype == torch.int16 else 1, int(labels.stride(0)),
+                                 int(labels.stride(1)), _p(part_hist), _p(part_sums), _p(hist), _p(sums), D, H, W, n, lo,
+                                 nb, _stream()), "dram_lobe_hist")
+    return hist, sums
+
+
 # --------------------------------------------------------------------------- heads / losses
 def head_fwd(x: Tensor, w: Tensor, bias: Tensor, lungs: Optional[Tensor], sigmoid: bool):
     """x [B,D,H,W,32] (float32 or bfloat16); w [NO,32]; lungs None or [B,Dl,Hl,Wl] full-res mask.  The dense maps

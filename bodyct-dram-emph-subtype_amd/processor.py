@@ -13,11 +13,13 @@ if not __package__:          # imported top-level (this directory on sys.path): 
     __package__ = _dropin.adopt(__name__)
 
 import json
+import math
+import re
 from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import transforms
+from . import ops, transforms
 from .models import CLE_RATIO_MAP, PSE_RATIO_MAP
 from .ops import _L, _chk, _p, _req, _stream
 
@@ -82,6 +84,108 @@ def region_metrics(table_row, names=None) -> dict:
     return out
 
 
+# --------------------------------------------------------------------------- per-lobe CT densitometry
+_DENSITO_KEY = re.compile(r"(laa\d+_fraction|perc\d+_hu|mean_lung_density|volume_ml)_per_(region|lung)")
+
+
+def densitometry_from_hist(hist: torch.Tensor, sums: torch.Tensor, spacing: Sequence[float],
+                           thresholds: Sequence[int] = (-950, -910), percentiles: Sequence[int] = (15,),
+                           hu_lo: int = -1024) -> dict:
+    """The tensor math of ``densitometry``: ``ops.lobe_histogram``'s (hist [n+1, nbins], sums [n+1, 2]) int64 -> the
+    result dict, O(rows * bins) torch operations on the tensors' own device (CPU tensors work), integer or float64
+    arithmetic, nothing read back."""
+    if hist.dim() != 2 or sums.dim() != 2 or hist.dtype != torch.int64 or sums.dtype != torch.int64 or \
+            hist.shape[0] < 2 or tuple(sums.shape) != (hist.shape[0], 2):
+        raise ValueError("densitometry: hist must be int64 [n_regions + 1, nbins] and sums int64 [n_regions + 1, 2]")
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3:
+        raise ValueError("densitometry: spacing must have three entries (z, y, x)")
+    nbins, lo = int(hist.shape[1]), int(hu_lo)
+    ts = [int(math.ceil(t)) for t in thresholds]           # #(hu < t) on integer HU = #(hu <= ceil(t) - 1)
+    for t in ts:
+        if not lo < t <= lo + nbins - 1:
+            raise ValueError(f"densitometry: threshold {t} is outside ({lo}, {lo + nbins - 1}]: its count would not be exact")
+    ps = list(percentiles)
+    for p in ps:
+        if int(p) != p or not 1 <= int(p) <= 99:
+            raise ValueError(f"densitometry: percentiles are integers in 1..99, got {p}")
+    ps = [int(p) for p in ps]
+    h = torch.cat([hist, hist.sum(0, keepdim=True)])       # the last row: the whole lung
+    s = torch.cat([sums, sums.sum(0, keepdim=True)])
+    vox = s[:, 0]
+    voxd = vox.double()
+    cdf = h.cumsum(1)                                      # #(clamped hu <= hu_lo + bin)
+    counts = torch.stack([cdf[:, t - 1 - lo] for t in ts]) if ts else h.new_zeros((0, h.shape[0]))
+    perc = torch.full((len(ps), h.shape[0]), float("nan"), dtype=torch.float64, device=h.device)
+    for i, p in enumerate(ps):
+        k = ((vox * p + 99) // 100).clamp_min(1)           # nearest rank: max(1, ceil(p N / 100))
+        idx = (cdf < k[:, None]).sum(1)                    # the first bin whose cumulative count reaches k
+        ok = (vox > 0) & (idx > 0) & (idx < nbins - 1)     # an end bin holds a tail: the value is only a bound
+        perc[i] = torch.where(ok, (idx + lo).double(), perc[i])
+    full = {"voxels": vox, "volume_ml": voxd * (sp[0] * sp[1] * sp[2]) / 1000.0, "mean_density": s[:, 1].double() / voxd,
+            "laa": counts.double() / voxd, "laa_counts": counts, "perc": perc}
+    out = {k: v[..., :-1] for k, v in full.items()}
+    out["whole_lung"] = {k: v[..., -1] for k, v in full.items()}
+    out["thresholds"], out["percentiles"], out["hu_lo"], out["nbins"] = tuple(ts), tuple(ps), lo, nbins
+    return out
+
+
+def densitometry(image: torch.Tensor, labels: torch.Tensor, spacing: Sequence[float], n_regions: int = 5,
+                 thresholds: Sequence[int] = (-950, -910), percentiles: Sequence[int] = (15,), hu_lo: int = -1024,
+                 nbins: int = 1024) -> dict:
+    """CT densitometry per lobe from ONE histogram pass (``ops.lobe_histogram``) over image [D,H,W] int16 HU and labels
+    [D,H,W] (``prepare_case(want_lobes=True)``'s 'image' and 'lobe_labels', at the scan's own resolution); spacing in
+    (z, y, x) mm.  Device tensors, rows 0..n_regions (row 0: lung voxels whose label is above n_regions; a label <= 0
+    is not lung):
+      'voxels' [n+1] int64; 'volume_ml' [n+1] float64 = voxels * sz*sy*sx / 1000; 'mean_density' [n+1] float64 (NaN for
+      an empty row); 'laa' [len(thresholds), n+1] float64 = #(hu < t) / voxels and 'laa_counts' (int64), every t in
+      (hu_lo, hu_lo + nbins - 1] so that the prefix sum is exact (else ValueError); 'perc' [len(percentiles), n+1]
+      float64: the smallest integer HU h with #(hu <= h) >= max(1, ceil(p N / 100)) (inverted CDF, nearest rank; p an
+      integer in 1..99), NaN for an empty row and where h falls in either end bin (the value is then only a bound);
+      'whole_lung': the same quantities over the sum of all rows.
+    Nothing is read back; ``densitometry_metrics`` formats the result on the host."""
+    hist, sums = ops.lobe_histogram(image, labels, n_regions, hu_lo, nbins)
+    return densitometry_from_hist(hist, sums, spacing, thresholds, percentiles, hu_lo)
+
+
+_densitometry = densitometry         # predict_case's switch has the function's name
+
+
+def densitometry_metrics(result: dict, names=None) -> dict:
+    """``densitometry``'s result -> entries of the metrics dict, beside ``region_metrics`` and keyed like it
+    (``names[label]`` of a mapping or sequence, else the label as a string): 'laa{|t|}_fraction_per_region' per
+    threshold and 'mean_lung_density_per_region' ("{:.3f}"), 'perc{p}_hu_per_region' ("{:d}"), 'volume_ml_per_region'
+    ("{:.1f}"), and their whole-lung twins ending '_per_lung' (one value each).  None (json null) stands for NaN.
+    Row 0 is not reported as a region.  Pure host code."""
+    def lst(v):
+        return v.tolist() if hasattr(v, "tolist") else v          # tensors, arrays and their scalars
+
+    def fmt(v, spec, cast=float):
+        return None if v is None or (isinstance(v, float) and math.isnan(v)) else spec.format(cast(v))
+
+    ts, ps = list(result["thresholds"]), list(result["percentiles"])
+    lung = result["whole_lung"]
+    cols = [(f"laa{abs(t)}_fraction", lst(result["laa"])[i], lst(lung["laa"])[i], "{:.3f}", float) for i, t in enumerate(ts)]
+    cols += [(f"perc{p}_hu", lst(result["perc"])[i], lst(lung["perc"])[i], "{:d}", int) for i, p in enumerate(ps)]
+    cols += [("mean_lung_density", lst(result["mean_density"]), lst(lung["mean_density"]), "{:.3f}", float),
+             ("volume_ml", lst(result["volume_ml"]), lst(lung["volume_ml"]), "{:.1f}", float)]
+    out = {}
+    for stem, per_row, whole, spec, cast in cols:
+        if len(per_row) < 2:
+            raise ValueError("densitometry_metrics: the result must hold rows 0..n_regions")
+        d = {}
+        for label in range(1, len(per_row)):
+            try:
+                key = str(names[label]) if names is not None else str(label)
+            except (KeyError, IndexError):
+                key = str(label)
+            d[key] = fmt(per_row[label], spec, cast)
+        out[f"{stem}_per_region"] = d
+    for stem, per_row, whole, spec, cast in cols:
+        out[f"{stem}_per_lung"] = fmt(whole, spec, cast)
+    return out
+
+
 def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=None) -> List[dict]:
     """processor.py:102-145 for a list of predict_step outputs: per scan the pasted CLE / PSE volumes (uint8 like
     the written .mha, and/or float) and the metrics entry of the results json.  A prediction that carries a
@@ -117,24 +221,44 @@ def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=No
 
 
 def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[float], target_size: Sequence[int],
-                 uid=None, want_u8: bool = True, regions: bool = False, region_names=None, **prepare_kw) -> dict:
+                 uid=None, want_u8: bool = True, regions: bool = False, region_names=None, densitometry: bool = False,
+                 densitometry_kw: Optional[dict] = None, **prepare_kw) -> dict:
     """One scan + its lobe segmentation -> its entry of ``build_outputs``: ``transforms.prepare_case`` (dataset.py:57-92)
     -> ``transforms.prepare_sample(target_size)`` -> a batch of one -> ``module.predict_step`` -> ``build_outputs``.
     The composition only; `prepare_kw` goes to ``prepare_case`` (crop_border, dilate_iterations, ...).  ``regions``:
     the lobe labels travel along (``prepare_case(want_lobes=True)``) and the entry carries the per-lobe metrics of
-    ``region_metrics``, keyed through ``region_names``."""
-    case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=bool(regions), **prepare_kw)
+    ``region_metrics``, keyed through ``region_names``.  ``densitometry``: the entry also carries
+    ``densitometry_metrics`` of the case's 'image' and 'lobe_labels' at the scan's own resolution (before the resize;
+    ``densitometry_kw`` goes to ``densitometry``), keyed through ``region_names`` as well, and a line in error_messages
+    when lung voxels carry a label above n_regions.  The two switches are independent: without ``regions`` the batch
+    holds no 'lobe_labels'."""
+    want_lobes = bool(regions) or bool(densitometry)
+    case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=want_lobes, **prepare_kw)
+    dens = None
+    if densitometry:
+        dens = _densitometry(case["image"], case["lobe_labels"], spacing, **(densitometry_kw or {}))
+        if not regions:
+            case = {k: v for k, v in case.items() if k != "lobe_labels"}
     sample = transforms.prepare_sample(case, target_size)
     keys = ("image", "lung_mask", "ess_mask", "crop_slice", "original_size") + (("lobe_labels",) if regions else ())
     batch = {k: sample[k].unsqueeze(0) for k in keys}
     batch["uid"] = [uid]
-    return build_outputs([module.predict_step(batch, 0)], want_u8=want_u8, region_names=region_names)[0]
+    entry = build_outputs([module.predict_step(batch, 0)], want_u8=want_u8, region_names=region_names)[0]
+    if dens is not None:
+        entry["metrics"].update(densitometry_metrics(dens, region_names))
+        outside = int(dens["voxels"][0])
+        if outside > 0:
+            entry["error_messages"].append("{:d} lung voxels carry a lobe label outside 1..{:d}: their density is in no "
+                                           "region".format(outside, dens["voxels"].shape[0] - 1))
+    return entry
 
 
 def write_reports(results: List[dict], centrilobular_json: Optional[str] = None, paraseptal_json: Optional[str] = None,
-                  output_json: Optional[str] = None, regions_json: Optional[str] = None):
+                  output_json: Optional[str] = None, regions_json: Optional[str] = None,
+                  densitometry_json: Optional[str] = None):
     """processor.py:160-177: the two single-scan score files and the results list; ``regions_json``: the regional
-    entries (``REGION_KEYS``) of the first result, which must carry them."""
+    entries (``REGION_KEYS``) of the first result, which must carry them; ``densitometry_json``: its densitometry
+    entries (``densitometry_metrics``), likewise."""
     m = results[0]["metrics"]
     if centrilobular_json:
         with open(centrilobular_json, "w") as f:
@@ -152,3 +276,10 @@ def write_reports(results: List[dict], centrilobular_json: Optional[str] = None,
             raise ValueError("write_reports: regions_json needs a result with regional metrics (predict_case(regions=True))")
         with open(regions_json, "w") as f:
             f.write(json.dumps({k: m[k] for k in REGION_KEYS}))
+    if densitometry_json:
+        keys = [k for k in m if _DENSITO_KEY.fullmatch(k)]
+        if "mean_lung_density_per_region" not in keys:
+            raise ValueError("write_reports: densitometry_json needs a result with densitometry metrics "
+                             "(predict_case(densitometry=True))")
+        with open(densitometry_json, "w") as f:
+            f.write(json.dumps({k: m[k] for k in keys}))

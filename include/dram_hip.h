@@ -668,6 +668,27 @@ int dram_case_prepare(const void* scan, const void* lobes, int lobe_dtype, void*
                       uint8_t* ess_mask, void* original, int D, int H, int W, int z0, int y0, int x0, int Dc, int Hc,
                       int Wc, int radius, int fill_value, int threshold, dram_stream_t stream);
 
+/* Per-lobe CT histogram of a prepared case (csrc/densito.hip): ONE pass over image [D,H,W] int16 HU (contiguous) and
+ * labels [D,H,W] of label_dtype 1 (uint8) or 2 (int16), read in place through stride_z / stride_y (in elements, >= 0;
+ * x stride 1), e.g. dram_case_prepare's image and the lung crop of the lobe volume.
+ *   hist [n_regions + 1][nbins] int64: voxels per row and 1-HU bin, bin = clamp(hu, hu_lo, hu_lo + nbins - 1) - hu_lo
+ *     (the two end bins collect the tails);
+ *   sums [n_regions + 1][2] int64 = { voxel count, sum of the raw (unclamped) HU values }.
+ *   Rows: label r in 1..n_regions -> row r; label <= 0 (signed for int16) is not lung and is counted nowhere; a label
+ *     above n_regions -> row 0 (lung that belongs to no region; no background there).  Sum over the rows = lobes > 0.
+ *   part_hist [nblk][n_regions + 1][nbins] int32 and part_sums [nblk][n_regions + 1][2] int64 scratch, nblk =
+ *     dram_lobe_hist_nblk(D*H*W): every workgroup writes all of its rows (no memset), a second launch folds them in
+ *     index order.  No global atomics, no ticket word, never synchronises, capturable; integer counts: bit-identical
+ *     from call to call.
+ * Null operand, label_dtype not 1 / 2, a size < 1, a negative stride, n_regions outside 1..15: DRAM_ERR_BAD_ARG.
+ * Supported: D*H*W < 2^31; nbins a multiple of 64 in 64..2048 with (n_regions + 1) * nbins <= 32768 (the counters of
+ * a workgroup live in LDS, 128 KiB at most); -32768 <= hu_lo and hu_lo + nbins - 1 <= 32767.  Anything else:
+ * DRAM_ERR_UNSUPPORTED. */
+int dram_lobe_hist_nblk(long long voxels);
+int dram_lobe_hist(const void* image, const void* labels, int label_dtype, long long stride_z, long long stride_y,
+                   int* part_hist, int64_t* part_sums, int64_t* hist, int64_t* sums, int D, int H, int W, int n_regions,
+                   int hu_lo, int nbins, dram_stream_t stream);
+
 /* Train-time augmentations (models.py:66-74) with GIVEN parameters, fused into one gather pass:
  * GaussianAddictive (intensity_transforms.py:145-177; noise [D,H,W] supplied by the caller, minmax[2] = volume
  * {min, max} on the device, e.g. folded from dram_minmax partials [nblk][2]), BoxMaskOut (:180-237), Flip
