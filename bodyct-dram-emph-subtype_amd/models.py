@@ -571,7 +571,8 @@ class ScanRegLightningModule(_ScanModule):
         A batch that holds 'lobe_labels' ([B,D,H,W] uint8 on the network grid, ``transforms.prepare_labels``) takes the
         fused tail (``ops.upproject_regions``: both heads and a per-region table in one pass) and returns in addition
         'region_table' [B, n+1, 4] float64 (rows 0..n: sum cle, sum pse, #ess, #voxels; row 0 = label 0 and labels above
-        n = ``args.n_regions``, default 5), 'cle_region_percentages' / 'pse_region_percentages' [B, n] (sum / #voxels of
+        n = the batch's optional 'n_regions' (an int, e.g. 2 x lobes for ``processor.core_peel``'s composite zone labels)
+        or else ``args.n_regions``, default 5), 'cle_region_percentages' / 'pse_region_percentages' [B, n] (sum / #voxels of
         that sample's region, NaN for an absent region), 'region_voxels' [B, n] and 'region_ess_fraction' [B, n]."""
         with torch.no_grad():
             scans = batch["image"].unsqueeze(1)
@@ -605,7 +606,7 @@ class ScanRegLightningModule(_ScanModule):
         dense_outs, _ = self.forward(scans, lungs)
         B = scans.shape[0]
         size = tuple(scans.shape[-3:])
-        n = int(getattr(self.args, "n_regions", 5))
+        n = int(batch["n_regions"]) if batch.get("n_regions") is not None else int(getattr(self.args, "n_regions", 5))
         heads = [d.reshape(B, *d.shape[-3:]) for d in dense_outs[:2]]          # channel views: no copy
         if B > 1 and heads[0].stride(0) != heads[1].stride(0):
             heads = [h.contiguous() for h in heads]

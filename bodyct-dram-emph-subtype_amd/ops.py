@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 import threading
 import weakref
@@ -1388,6 +1389,85 @@ def lobe_histogram(image: Tensor, labels: Tensor, n_regions: int = 5, hu_lo: int
                                  int(labels.stride(1)), _p(part_hist), _p(part_sums), _p(hist), _p(sums), D, H, W, n, lo,
                                  nb, _stream()), "dram_lobe_hist")
     return hist, sums
+
+
+EDT_FULL_UM = 1 << 26           # max_um from here on is the full transform (no distance in a supported volume reaches it)
+
+
+def lung_zones_units(spacing, peel_mm, max_mm=None):
+    """(spacing in whole micrometres (z, y, x), peel_um, max_um) of ``lung_zones``: round(mm * 1000), ``max_mm=None``
+    -> peel_mm, ``inf`` (or anything from 2^26 um on) -> ``EDT_FULL_UM``.  ValueError for a spacing or peel_mm that is
+    not positive and finite, a spacing outside 1..20000 um, and max_mm < peel_mm.  Pure host code."""
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3:
+        raise ValueError("lung_zones: spacing must have three entries (z, y, x)")
+    if not all(math.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f"lung_zones: spacing must be positive and finite, got {tuple(sp)}")
+    s_um = [int(round(v * 1000.0)) for v in sp]
+    if not all(1 <= s <= 20000 for s in s_um):
+        raise ValueError(f"lung_zones: spacing must round to 1..20000 um per axis, got {tuple(sp)} mm")
+    peel = float(peel_mm)
+    if not (math.isfinite(peel) and peel > 0):
+        raise ValueError(f"lung_zones: peel_mm must be positive and finite, got {peel_mm}")
+    peel_um = min(int(round(peel * 1000.0)), EDT_FULL_UM)
+    if max_mm is None:
+        max_um = peel_um
+    else:
+        mx = float(max_mm)
+        if math.isnan(mx) or mx < peel:
+            raise ValueError(f"lung_zones: max_mm {max_mm} must be at least peel_mm {peel_mm}")
+        max_um = EDT_FULL_UM if math.isinf(mx) else min(int(round(mx * 1000.0)), EDT_FULL_UM)
+    return tuple(s_um), peel_um, max(max_um, peel_um)
+
+
+def lung_zones(labels: Tensor, spacing, peel_mm: float, n_regions: Optional[int] = None, max_mm: Optional[float] = None,
+               want_dist: bool = False):
+    """Core / peel zones of the lung from the exact Euclidean distance transform of ``labels > 0`` at the scan's own
+    anisotropic spacing (csrc/edt.hip; definitions: INTEGRATION.md B7).
+
+    labels [D,H,W] uint8 / int16 / bool, read in place through their z / y strides when the x stride is 1
+    (``prepare_case``'s 'lobe_labels' view; any other view is made contiguous first); spacing (z, y, x) and peel_mm in
+    mm, taken in whole micrometres.  d2 = squared distance to the centre of the nearest background voxel OF THE VOLUME
+    (nothing outside it is background), an integer in um^2; ``max_mm``: distances above it are +inf (None: peel_mm, the
+    least work that decides the zones; inf: the full transform).  -> (zones, zone_labels | None, dist_mm | None):
+      zones uint8: 0 not lung, 1 peel (d2 <= peel_um^2), 2 core;
+      zone_labels uint8 (with ``n_regions`` = n in 1..7): label r in 1..n -> r + n * (zone - 1), a lung label above n ->
+        255 -- the label volume of ``lobe_histogram`` / ``upproject_regions`` with 2 n regions;
+      dist_mm float32 (``want_dist``): sqrt(d2) / 1000, 0 outside the lung, +inf where d2 is.
+    Supported: fewer than 2^31 voxels, spacing 1..20000 um and (size - 1) * spacing < 2^25 um on every axis.  Exact
+    integers: bit-identical from call to call; never synchronises; every check runs before any launch."""
+    if not isinstance(labels, Tensor) or labels.dim() != 3 or min(labels.shape) < 1:
+        raise ValueError("lung_zones: labels must be a non-empty [D,H,W] tensor")
+    if labels.dtype == torch.bool:
+        labels = labels.view(torch.uint8)
+    if labels.dtype not in (torch.uint8, torch.int16):
+        raise TypeError(f"lung_zones: expected uint8, int16 or bool labels, got {labels.dtype}")
+    s_um, peel_um, max_um = lung_zones_units(spacing, peel_mm, max_mm)
+    n = 0
+    if n_regions is not None:
+        n = int(n_regions)
+        if not 1 <= n <= 7:
+            raise ValueError(f"lung_zones: n_regions must be 1..7 (2 n <= 15 rows downstream), got {n_regions}")
+    D, H, W = (int(v) for v in labels.shape)
+    if D * H * W >= 2 ** 31:
+        raise ValueError("lung_zones: volumes of 2^31 voxels or more are not supported")
+    for size, s, axis in zip((D, H, W), s_um, "zyx"):
+        if (size - 1) * s >= 2 ** 25:
+            raise ValueError(f"lung_zones: axis {axis}: (size - 1) * spacing = {(size - 1) * s} um must be below 2^25")
+    if (W > 1 and labels.stride(2) != 1) or min(labels.stride()) < 0:
+        labels = labels.contiguous()
+    dev = labels.device
+    with launch_scope(dev):
+        _req(labels[0, 0], "lung_zones: labels", labels.dtype)           # device; a row is contiguous
+        nbytes = int(_L().dram_lung_zones_workspace(D, H, W, max_um))
+        work = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+        zones = torch.empty((D, H, W), device=dev, dtype=torch.uint8)
+        zlab = torch.empty((D, H, W), device=dev, dtype=torch.uint8) if n else None
+        dist = torch.empty((D, H, W), device=dev, dtype=torch.float32) if want_dist else None
+        _chk(_L().dram_lung_zones(_p(labels), 2 if labels.dtype == torch.int16 else 1, int(labels.stride(0)),
+                                  int(labels.stride(1)), _p(zones), _p(zlab), _p(dist), _p(work), D, H, W, *s_um, peel_um,
+                                  max_um, n, _stream()), "dram_lung_zones")
+    return zones, zlab, dist
 
 
 # --------------------------------------------------------------------------- heads / losses

@@ -186,6 +186,96 @@ def densitometry_metrics(result: dict, names=None) -> dict:
     return out
 
 
+# --------------------------------------------------------------------------- core / peel split of the per-lobe report
+ZONES = ("peel", "core")
+_CORE_PEEL_KEY = re.compile(r"((laa\d+_fraction|perc\d+_hu|mean_lung_density|volume_ml|(cle|pse)_lesion_percentage)"
+                            r"_per_(region|lung)|region_voxels)_(peel|core)|peel_mm")
+
+
+def core_peel(image: torch.Tensor, labels: torch.Tensor, spacing: Sequence[float], peel_mm: float = 10.0,
+              n_regions: int = 5, **densitometry_kw) -> dict:
+    """``densitometry`` of every lobe split into its subpleural rind (the "peel": lung voxels within ``peel_mm`` of the
+    nearest non-lung voxel of the crop, Euclidean, at the scan's own spacing) and the rest (the "core"):
+    ``ops.lung_zones`` -> composite labels (1..n the peel, n+1..2n the core of lobe r) -> ONE ``ops.lobe_histogram``
+    with 2n rows -> ``densitometry_from_hist`` on each zone's rows behind a zero row 0, so that each zone also has its
+    'whole_lung'.  ``peel_mm`` is the caller's choice -- the 10 mm default is a common rind width, not a recommendation;
+    ``n_regions`` 1..7; ``densitometry_kw``: thresholds, percentiles, hu_lo, nbins.  ->
+      {'peel': <densitometry result>, 'core': <densitometry result>, 'outside_voxels': int64 0-dim (lung voxels whose
+       label is above n_regions: row 0 of the composite histogram, in neither zone's rows), 'zones', 'zone_labels'
+       (uint8 [D,H,W], ``ops.lung_zones``), 'peel_mm', 'n_regions'}.
+    The field of view is no pleura: a lung cut by the crop has no peel there.  Device tensors, nothing read back."""
+    n = int(n_regions)
+    if not isinstance(image, torch.Tensor) or not isinstance(labels, torch.Tensor) or tuple(image.shape) != tuple(labels.shape):
+        raise ValueError("core_peel: image and labels must be tensors of one [D,H,W] shape")
+    kw = dict(densitometry_kw)
+    hu_lo, nbins = int(kw.pop("hu_lo", -1024)), int(kw.pop("nbins", 1024))
+    zones, zone_labels, _ = ops.lung_zones(labels, spacing, peel_mm, n_regions=n)
+    hist, sums = ops.lobe_histogram(image, zone_labels, 2 * n, hu_lo, nbins)
+    out = {}
+    for i, zone in enumerate(ZONES):
+        rows = slice(1 + i * n, 1 + (i + 1) * n)
+        out[zone] = densitometry_from_hist(torch.cat([torch.zeros_like(hist[:1]), hist[rows]]),
+                                           torch.cat([torch.zeros_like(sums[:1]), sums[rows]]), spacing, hu_lo=hu_lo, **kw)
+    out.update(outside_voxels=sums[0, 0], zones=zones, zone_labels=zone_labels, peel_mm=float(peel_mm), n_regions=n)
+    return out
+
+
+_core_peel = core_peel               # predict_case's switch has the function's name
+
+
+def core_peel_metrics(result: dict, names=None) -> dict:
+    """``core_peel``'s result -> entries of the metrics dict: ``densitometry_metrics`` of each zone with the zone's name
+    appended to every key ('laa950_fraction_per_region_peel', 'volume_ml_per_lung_core', ...: the same formats, keyed
+    through ``names`` the same way, None for NaN), and 'peel_mm' ("{:.3f}").  Pure host code."""
+    out = {}
+    for zone in ZONES:
+        out.update({f"{k}_{zone}": v for k, v in densitometry_metrics(result[zone], names).items()})
+    out["peel_mm"] = "{:.3f}".format(float(result["peel_mm"]))
+    return out
+
+
+def fold_zone_table(table_row) -> torch.Tensor:
+    """The composite region table [2n+1, 4] (rows 1..n peel, n+1..2n core) -> the per-lobe one [n+1, 4] that
+    ``region_metrics`` reads, in float64 on the host: row r = row r + row n+r, row 0 stays row 0."""
+    t = torch.as_tensor(table_row).detach().cpu().double()
+    if t.dim() != 2 or t.shape[1] != 4 or t.shape[0] < 3 or t.shape[0] % 2 != 1:
+        raise ValueError("fold_zone_table: table_row must be [2 * n_regions + 1, 4]")
+    n = (t.shape[0] - 1) // 2
+    return torch.cat([t[:1], t[1:n + 1] + t[n + 1:]])
+
+
+def zone_region_metrics(table_row, names=None) -> dict:
+    """One sample's composite region table [2n+1, 4] (predict_step's 'region_table'[b] for ``core_peel``'s zone labels
+    and 'n_regions' = 2n) -> for each zone Z in ('peel', 'core') 'cle_lesion_percentage_per_region_Z',
+    'pse_lesion_percentage_per_region_Z' and 'region_voxels_Z' (keyed and formatted like ``region_metrics``; None for
+    a lobe without voxels in that zone) and 'cle_lesion_percentage_per_lung_Z' / 'pse_lesion_percentage_per_lung_Z' =
+    sum / voxels over the zone's rows (None for an empty zone).  No severity scores: the ratio bands are defined per
+    lung.  Pure host code, float64."""
+    rows = table_row.tolist() if torch.is_tensor(table_row) else [list(r) for r in table_row]
+    if len(rows) < 3 or len(rows) % 2 != 1 or any(len(r) != 4 for r in rows):
+        raise ValueError("zone_region_metrics: table_row must be [2 * n_regions + 1, 4]")
+    n = (len(rows) - 1) // 2
+    out = {}
+    for i, zone in enumerate(ZONES):
+        per = {f"{h}_lesion_percentage_per_region_{zone}": {} for h in ("cle", "pse")}
+        per[f"region_voxels_{zone}"] = {}
+        tot = [0.0, 0.0, 0.0]
+        for label in range(1, n + 1):
+            try:
+                key = str(names[label]) if names is not None else str(label)
+            except (KeyError, IndexError):
+                key = str(label)
+            s_cle, s_pse, _, n_vox = (float(v) for v in rows[i * n + label])
+            for h, s in (("cle", s_cle), ("pse", s_pse)):
+                per[f"{h}_lesion_percentage_per_region_{zone}"][key] = "{:.3f}".format(s / n_vox) if n_vox > 0 else None
+            per[f"region_voxels_{zone}"][key] = "{:d}".format(int(round(n_vox)))
+            tot = [tot[0] + s_cle, tot[1] + s_pse, tot[2] + n_vox]
+        out.update(per)
+        for h, s in (("cle", tot[0]), ("pse", tot[1])):
+            out[f"{h}_lesion_percentage_per_lung_{zone}"] = "{:.3f}".format(s / tot[2]) if tot[2] > 0 else None
+    return out
+
+
 def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=None) -> List[dict]:
     """processor.py:102-145 for a list of predict_step outputs: per scan the pasted CLE / PSE volumes (uint8 like
     the written .mha, and/or float) and the metrics entry of the results json.  A prediction that carries a
@@ -222,7 +312,8 @@ def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=No
 
 def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[float], target_size: Sequence[int],
                  uid=None, want_u8: bool = True, regions: bool = False, region_names=None, densitometry: bool = False,
-                 densitometry_kw: Optional[dict] = None, **prepare_kw) -> dict:
+                 densitometry_kw: Optional[dict] = None, core_peel: bool = False, peel_mm: float = 10.0,
+                 **prepare_kw) -> dict:
     """One scan + its lobe segmentation -> its entry of ``build_outputs``: ``transforms.prepare_case`` (dataset.py:57-92)
     -> ``transforms.prepare_sample(target_size)`` -> a batch of one -> ``module.predict_step`` -> ``build_outputs``.
     The composition only; `prepare_kw` goes to ``prepare_case`` (crop_border, dilate_iterations, ...).  ``regions``:
@@ -231,34 +322,69 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     ``densitometry_metrics`` of the case's 'image' and 'lobe_labels' at the scan's own resolution (before the resize;
     ``densitometry_kw`` goes to ``densitometry``), keyed through ``region_names`` as well, and a line in error_messages
     when lung voxels carry a label above n_regions.  The two switches are independent: without ``regions`` the batch
-    holds no 'lobe_labels'."""
-    want_lobes = bool(regions) or bool(densitometry)
+    holds no 'lobe_labels'.
+
+    ``core_peel`` (independent of both): every per-lobe number is split into the subpleural rind of ``peel_mm`` (the
+    caller's choice) and the rest.  Scan side: ``core_peel_metrics`` of ``core_peel`` on the crop before the resize
+    (n_regions = ``module.args.n_regions``, default 5; thresholds, percentiles, hu_lo, nbins from ``densitometry_kw``).
+    Network side: the composite zone labels travel as the batch's 'lobe_labels' with 'n_regions' = 2n, the one fused
+    tail gives a [2n+1, 4] table, and the entry carries ``zone_region_metrics`` of it; with ``regions`` the table
+    ``region_metrics`` reads is that one folded on the host (``fold_zone_table``).  A line in error_messages when lung
+    voxels carry a label above n_regions.  'full_cle' / 'full_pse' are the same bit for bit under every combination."""
+    want_lobes = bool(regions) or bool(densitometry) or bool(core_peel)
     case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=want_lobes, **prepare_kw)
-    dens = None
+    dens = cp = None
     if densitometry:
         dens = _densitometry(case["image"], case["lobe_labels"], spacing, **(densitometry_kw or {}))
-        if not regions:
-            case = {k: v for k, v in case.items() if k != "lobe_labels"}
+    if core_peel:
+        n = int(getattr(module.args, "n_regions", 5))
+        kw = dict(densitometry_kw or {})
+        if int(kw.pop("n_regions", n)) != n:
+            raise ValueError(f"predict_case: core_peel splits the module's n_regions = {n} lobes; densitometry_kw asks "
+                             "for another count")
+        cp = _core_peel(case["image"], case["lobe_labels"], spacing, peel_mm, n, **kw)
+        case = dict(case, lobe_labels=cp["zone_labels"])
+    elif not regions:
+        case = {k: v for k, v in case.items() if k != "lobe_labels"}
     sample = transforms.prepare_sample(case, target_size)
-    keys = ("image", "lung_mask", "ess_mask", "crop_slice", "original_size") + (("lobe_labels",) if regions else ())
+    labelled = bool(regions) or bool(core_peel)
+    keys = ("image", "lung_mask", "ess_mask", "crop_slice", "original_size") + (("lobe_labels",) if labelled else ())
     batch = {k: sample[k].unsqueeze(0) for k in keys}
     batch["uid"] = [uid]
-    entry = build_outputs([module.predict_step(batch, 0)], want_u8=want_u8, region_names=region_names)[0]
+    zone_metrics = None
+    if cp is not None:
+        batch["n_regions"] = 2 * cp["n_regions"]
+    pred = module.predict_step(batch, 0)
+    if cp is not None:
+        composite = pred["region_table"][0].cpu()
+        zone_metrics = zone_region_metrics(composite, region_names)
+        pred = {k: v for k, v in pred.items() if k != "region_table"}
+        if regions:
+            pred["region_table"] = fold_zone_table(composite).unsqueeze(0)
+    entry = build_outputs([pred], want_u8=want_u8, region_names=region_names)[0]
     if dens is not None:
         entry["metrics"].update(densitometry_metrics(dens, region_names))
         outside = int(dens["voxels"][0])
         if outside > 0:
             entry["error_messages"].append("{:d} lung voxels carry a lobe label outside 1..{:d}: their density is in no "
                                            "region".format(outside, dens["voxels"].shape[0] - 1))
+    if cp is not None:
+        entry["metrics"].update(core_peel_metrics(cp, region_names))
+        entry["metrics"].update(zone_metrics)
+        outside = int(cp["outside_voxels"])
+        if outside > 0:
+            entry["error_messages"].append("{:d} lung voxels carry a lobe label outside 1..{:d}: they are in no region's "
+                                           "peel or core".format(outside, cp["n_regions"]))
     return entry
 
 
 def write_reports(results: List[dict], centrilobular_json: Optional[str] = None, paraseptal_json: Optional[str] = None,
                   output_json: Optional[str] = None, regions_json: Optional[str] = None,
-                  densitometry_json: Optional[str] = None):
+                  densitometry_json: Optional[str] = None, core_peel_json: Optional[str] = None):
     """processor.py:160-177: the two single-scan score files and the results list; ``regions_json``: the regional
     entries (``REGION_KEYS``) of the first result, which must carry them; ``densitometry_json``: its densitometry
-    entries (``densitometry_metrics``), likewise."""
+    entries (``densitometry_metrics``), likewise; ``core_peel_json``: its ``core_peel_metrics`` and
+    ``zone_region_metrics`` entries, likewise."""
     m = results[0]["metrics"]
     if centrilobular_json:
         with open(centrilobular_json, "w") as f:
@@ -282,4 +408,11 @@ def write_reports(results: List[dict], centrilobular_json: Optional[str] = None,
             raise ValueError("write_reports: densitometry_json needs a result with densitometry metrics "
                              "(predict_case(densitometry=True))")
         with open(densitometry_json, "w") as f:
+            f.write(json.dumps({k: m[k] for k in keys}))
+    if core_peel_json:
+        keys = [k for k in m if _CORE_PEEL_KEY.fullmatch(k)]
+        if "mean_lung_density_per_region_peel" not in keys or "region_voxels_peel" not in keys or "peel_mm" not in keys:
+            raise ValueError("write_reports: core_peel_json needs a result with core / peel metrics "
+                             "(predict_case(core_peel=True))")
+        with open(core_peel_json, "w") as f:
             f.write(json.dumps({k: m[k] for k in keys}))

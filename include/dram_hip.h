@@ -689,6 +689,32 @@ int dram_lobe_hist(const void* image, const void* labels, int label_dtype, long 
                    int* part_hist, int64_t* part_sums, int64_t* hist, int64_t* sums, int D, int H, int W, int n_regions,
                    int hu_lo, int nbins, dram_stream_t stream);
 
+/* Core / peel zones of the lung from an exact 3-D Euclidean distance transform (csrc/edt.hip).  labels [D,H,W] of
+ * label_dtype 1 (uint8) or 2 (int16), read in place through stride_z / stride_y (in elements, >= 0; x stride 1) like
+ * dram_lobe_hist's; lung = label > 0 (signed for int16), background = every other voxel of the volume, and nothing
+ * outside the volume is background.  All distance arithmetic is in integers: s*_um the spacing in whole micrometres,
+ *   d2(v) = min over background voxels u of sum_a (s_a (v_a - u_a))^2   [um^2, to the centre of the voxel u],
+ * +inf when the volume holds no background or none within max_um (d2 > max_um^2).  max_um >= 2^26 is the full
+ * transform: no distance in a supported volume reaches it.
+ *   zones [D,H,W] uint8: 0 not lung, 1 peel (d2 <= peel_um^2, equality included), 2 core (+inf included);
+ *   zone_labels [D,H,W] uint8, optional (NULL, and then n_regions = 0): 0 not lung; a lung voxel with label r in
+ *     1..n_regions -> r + n_regions * (zone - 1), so 1..n is the peel and n+1..2n the core of region r; a lung label
+ *     above n_regions -> 255 (row 0 of dram_lobe_hist / dram_upproject_regions called with 2 n regions);
+ *   dist_mm [D,H,W] float32, optional (NULL): float(sqrt(double(d2)) / 1000.0), 0 outside the lung, +inf with d2;
+ *   workspace: dram_lung_zones_workspace(D, H, W, max_um) bytes (two work volumes of uint32 when max_um <= 65535, else
+ *     of uint64; 0 for sizes the call refuses), 256-byte aligned, owned by the caller; needs no clearing.
+ * Three launches (x, y, z passes); every output element and every workspace element that is read is written by them.
+ * No global atomics, no ticket word, no waiting between workgroups, never synchronises, capturable; integer minima:
+ * bit-identical from call to call.
+ * Null labels / zones / workspace, label_dtype not 1 / 2, a size < 1, a negative stride, peel_um < 0, max_um < peel_um,
+ * n_regions outside 1..7 with zone_labels (2 n <= 15) or non-zero without: DRAM_ERR_BAD_ARG.  Supported: D*H*W < 2^31,
+ * 1 <= s_a <= 20000 and (n_a - 1) * s_a < 2^25 on every axis (every d2 is then below 2^53: exact in int64 and in
+ * double).  Anything else: DRAM_ERR_UNSUPPORTED. */
+long long dram_lung_zones_workspace(int D, int H, int W, long long max_um);
+int dram_lung_zones(const void* labels, int label_dtype, long long stride_z, long long stride_y, uint8_t* zones,
+                    uint8_t* zone_labels, float* dist_mm, void* workspace, int D, int H, int W, int sz_um, int sy_um,
+                    int sx_um, long long peel_um, long long max_um, int n_regions, dram_stream_t stream);
+
 /* Train-time augmentations (models.py:66-74) with GIVEN parameters, fused into one gather pass:
  * GaussianAddictive (intensity_transforms.py:145-177; noise [D,H,W] supplied by the caller, minmax[2] = volume
  * {min, max} on the device, e.g. folded from dram_minmax partials [nblk][2]), BoxMaskOut (:180-237), Flip
