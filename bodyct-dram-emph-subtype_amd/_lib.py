@@ -24,7 +24,7 @@ from . import _build
 _SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong,
             "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
             "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
-_POINTEES = set(_SCALARS) | {"void", "char", "uint8_t"}      # ... and the header's structs; any pointer is a c_void_p
+_POINTEES = set(_SCALARS) | {"void", "char", "uint8_t", "int16_t"}     # ... and the header's structs; any pointer is a c_void_p
 _ID = r"[A-Za-z_]\w*"
 _DECLARATOR = re.compile(rf"(const\s+)?({_ID}(?:\s+{_ID})*?)(?:\s*(\*)\s*|\s+)({_ID})((?:\s*\[\d+\])*)")
 _FUNCTION = re.compile(rf"(const\s+char\s*\*|{_ID}(?:\s+{_ID})*?\s)\s*(dram_\w+)\s*\((.*)\)", re.S)

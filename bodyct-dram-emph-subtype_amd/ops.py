@@ -1470,6 +1470,91 @@ def lung_zones(labels: Tensor, spacing, peel_mm: float, n_regions: Optional[int]
     return zones, zlab, dist
 
 
+CCL_TABLE_COLS = 35             # 32 size bins (2^k <= size < 2^(k+1)), components, foreground voxels, largest size
+
+
+def _label_volume(t, fn: str, name: str) -> Tensor:
+    """A key / label operand of the component labelling: a non-empty [D,H,W] tensor of bool / uint8 / int16, bool seen
+    as uint8.  Type and shape only: nothing here touches the device."""
+    if not isinstance(t, Tensor) or t.dim() != 3 or min(t.shape) < 1:
+        raise ValueError(f"{fn}: {name} must be a non-empty [D,H,W] tensor")
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dtype not in (torch.uint8, torch.int16):
+        raise TypeError(f"{fn}: expected uint8, int16 or bool {name}, got {t.dtype}")
+    return t
+
+
+def _label_components(fn: str, labels: Tensor, image: Optional[Tensor], threshold: int, by_lobe: bool, connectivity: int,
+                      n_regions: int, want_sizes: bool):
+    n, conn = int(n_regions), int(connectivity)
+    if conn not in (6, 26):
+        raise ValueError(f"{fn}: connectivity must be 6 or 26, got {connectivity}")
+    if not 1 <= n <= 15:
+        raise ValueError(f"{fn}: n_regions must be 1..15, got {n_regions}")
+    D, H, W = (int(v) for v in labels.shape)
+    if D * H * W >= 2 ** 31:
+        raise ValueError(f"{fn}: volumes of 2^31 voxels or more are not supported")
+    if (W > 1 and labels.stride(2) != 1) or min(labels.stride()) < 0:
+        labels = labels.contiguous()
+    dev = labels.device
+    with launch_scope(dev):
+        _req(labels[0, 0], f"{fn}: {'labels' if image is not None else 'key'}", labels.dtype)   # a row is contiguous
+        if image is not None:
+            _req(image, f"{fn}: image", torch.int16)
+        nbytes = int(_L().dram_label_components_workspace(D, H, W))
+        work = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+        comp = torch.empty((D, H, W), device=dev, dtype=torch.int32)
+        sizes = torch.empty((D, H, W), device=dev, dtype=torch.int32) if want_sizes else None
+        table = torch.empty((n + 1, CCL_TABLE_COLS), device=dev, dtype=torch.int64)
+        _chk(_L().dram_label_components(_p(labels), 2 if labels.dtype == torch.int16 else 1, int(labels.stride(0)),
+                                        int(labels.stride(1)), _p(image), int(threshold), 1 if by_lobe else 0, conn, n,
+                                        _p(comp), _p(sizes), _p(table), _p(work), D, H, W, _stream()),
+             "dram_label_components")
+    return comp, table, sizes
+
+
+def label_components(key: Tensor, connectivity: int = 6, n_regions: int = 5, want_sizes: bool = False):
+    """Connected components of a 3-D key volume (csrc/ccl.hip; definitions: INTEGRATION.md B8).
+
+    key [D,H,W] uint8 / int16 / bool, read in place through its z / y strides when the x stride is 1 (any other view is
+    made contiguous first): 0 (or below) is background, two voxels are connected when they are neighbours under
+    ``connectivity`` (6 faces; 26 faces, edges, corners) and carry the same non-zero key.  -> (components, table,
+    cluster_voxels | None):
+      components int32 [D,H,W]: the linear index (z*H + y)*W + x of the component's smallest voxel, -1 on background;
+      table int64 [n_regions + 1, 35]: a component counts in the row of its key (key r in 1..n_regions -> row r, a key
+        above n_regions -> row 0); columns 0..31 the components with 2^k <= size < 2^(k+1), 32 the number of components,
+        33 the foreground voxels, 34 the largest size;
+      cluster_voxels int32 [D,H,W] (``want_sizes``): the size of the voxel's component, 0 on background.
+    Fewer than 2^31 voxels.  Integer atomics only: bit-identical from call to call; never synchronises; every check runs
+    before any launch."""
+    key = _label_volume(key, "label_components", "key")
+    return _label_components("label_components", key, None, 0, True, connectivity, n_regions, want_sizes)
+
+
+def laa_components(image: Tensor, labels: Tensor, threshold: int = -950, n_regions: int = 5, connectivity: int = 6,
+                   by_lobe: bool = True, want_sizes: bool = False):
+    """Low-attenuation clusters of a scan: ``label_components`` of the LAA key, formed inside the kernel.
+
+    image [D,H,W] int16 HU, contiguous; labels [D,H,W] uint8 / int16 / bool of the same shape, read in place like
+    ``lobe_histogram``'s.  The key is ``labels`` where ``labels > 0`` and ``image < threshold`` (strict, the comparison
+    of ``densitometry``'s 'laa_counts'), else 0 -- clusters do not cross a fissure, each belongs to one lobe -- or, with
+    ``by_lobe=False``, 1 there: whole-lung clusters, reported in row 1 of a table of two rows.  threshold: an integer HU
+    in -32768..32768.  -> the triple of ``label_components``."""
+    labels = _label_volume(labels, "laa_components", "labels")
+    if not isinstance(image, Tensor) or image.dim() != 3:
+        raise ValueError("laa_components: image must be a [D,H,W] tensor")
+    if image.dtype != torch.int16:
+        raise TypeError(f"laa_components: expected an int16 image, got {image.dtype}")
+    if tuple(labels.shape) != tuple(image.shape):
+        raise ValueError(f"laa_components: labels {tuple(labels.shape)} must have the image's shape {tuple(image.shape)}")
+    t = int(threshold)
+    if t != threshold or not -32768 <= t <= 32768:
+        raise ValueError(f"laa_components: threshold must be an integer HU in -32768..32768, got {threshold}")
+    return _label_components("laa_components", labels, image, t, bool(by_lobe), connectivity,
+                             n_regions if by_lobe else 1, want_sizes)
+
+
 # --------------------------------------------------------------------------- heads / losses
 def head_fwd(x: Tensor, w: Tensor, bias: Tensor, lungs: Optional[Tensor], sigmoid: bool):
     """x [B,D,H,W,32] (float32 or bfloat16); w [NO,32]; lungs None or [B,Dl,Hl,Wl] full-res mask.  The dense maps

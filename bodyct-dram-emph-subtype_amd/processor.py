@@ -276,6 +276,104 @@ def zone_region_metrics(table_row, names=None) -> dict:
     return out
 
 
+# --------------------------------------------------------------------------- LAA cluster analysis per lobe
+_CLUSTER_KEY = re.compile(r"laa\d+_(clusters|largest_cluster_ml|cluster_d)_per_(region|lung)|laa_cluster_connectivity")
+
+
+def clusters_from_table(table: torch.Tensor, spacing: Sequence[float]) -> dict:
+    """The tensor math of ``laa_clusters``: ``ops.label_components``' table int64 [n+1, 35] -> per row 'clusters',
+    'voxels', 'largest_voxels' (int64 [n+1]), 'largest_ml' = largest_voxels * sz*sy*sx / 1000 and 'mean_voxels' =
+    voxels / clusters (float64, NaN for an empty row), 'size_hist' [n+1, 32] (clusters with 2^k <= size < 2^(k+1)) and
+    'd' (float64 [n+1]): with kmax the highest non-empty bin and Y_k = sum_{j >= k} size_hist[j] (the clusters of at
+    least 2^k voxels, exact) for k = 0..kmax, D = -slope of the least-squares line through (k ln 2, ln Y_k); NaN when
+    kmax < 2 (fewer than three points).  O(rows * 32) torch operations on the table's own device (CPU tensors work),
+    int64 / float64 arithmetic, nothing read back."""
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.int64 or \
+            table.shape[0] < 2 or table.shape[1] != ops.CCL_TABLE_COLS:
+        raise ValueError(f"clusters_from_table: table must be int64 [n_regions + 1, {ops.CCL_TABLE_COLS}]")
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3:
+        raise ValueError("clusters_from_table: spacing must have three entries (z, y, x)")
+    nan = float("nan")
+    hist = table[:, :32]
+    count, vox, largest = table[:, 32], table[:, 33], table[:, 34]
+    some = count > 0
+    nan_row = torch.full_like(count, nan, dtype=torch.float64)
+    largest_ml = torch.where(some, largest.double() * (sp[0] * sp[1] * sp[2]) / 1000.0, nan_row)
+    mean_vox = torch.where(some, vox.double() / count.clamp_min(1).double(), nan_row)
+    k = torch.arange(32, device=table.device)
+    kmax = ((hist > 0) * k).amax(1)                                   # 0 for an empty row as well: NaN either way
+    y = hist.flip(1).cumsum(1).flip(1)                                # Y_k, exact
+    pts = (k[None, :] <= kmax[:, None]) & some[:, None]               # the points k = 0..kmax of a row
+    w = pts.double()
+    npts = w.sum(1)
+    xs = k.double()[None, :] * math.log(2.0)
+    ys = torch.where(pts, y.clamp_min(1).double().log(), torch.zeros_like(w))
+    xm = (w * xs).sum(1) / npts.clamp_min(1.0)
+    ym = (w * ys).sum(1) / npts.clamp_min(1.0)
+    dx = (xs - xm[:, None]) * w
+    sxx = (dx * dx).sum(1)
+    sxy = (dx * (ys - ym[:, None])).sum(1)
+    d = torch.where(npts >= 3, -sxy / sxx.clamp_min(1e-300), nan_row) + 0.0          # + 0.0: a flat line gives 0, not -0
+    return {"clusters": count, "voxels": vox, "largest_voxels": largest, "largest_ml": largest_ml,
+            "mean_voxels": mean_vox, "size_hist": hist, "d": d}
+
+
+def laa_clusters(image: torch.Tensor, labels: torch.Tensor, spacing: Sequence[float], n_regions: int = 5,
+                 threshold: int = -950, connectivity: int = 6) -> dict:
+    """How the low attenuation of every lobe is arranged: the connected clusters of ``image <
+    threshold`` inside each lobe (``ops.laa_components(by_lobe=True)``: a cluster never crosses a fissure) ->
+    ``clusters_from_table`` for the rows 0..n_regions (row 0: LAA voxels whose label is above n_regions), and once more
+    over the whole lung (``by_lobe=False``: clusters may cross fissures), whose one row is 'whole_lung'.  Also
+    'threshold', 'connectivity' and 'components', the per-lobe id volume (int32, -1 outside the clusters).  'd' is the
+    exponent of the cumulative cluster-size distribution sampled at powers of two -- NOT Mishima's per-slice 2-D fit
+    over every distinct size.  Device tensors, nothing read back; ``laa_cluster_metrics`` formats it on the host."""
+    comp, table, _ = ops.laa_components(image, labels, threshold, n_regions, connectivity, by_lobe=True)
+    _, whole, _ = ops.laa_components(image, labels, threshold, 1, connectivity, by_lobe=False)
+    out = clusters_from_table(table, spacing)
+    out["whole_lung"] = {k: v[1] for k, v in clusters_from_table(whole, spacing).items()}
+    out.update(threshold=int(threshold), connectivity=int(connectivity), components=comp)
+    return out
+
+
+def laa_cluster_metrics(result: dict, names=None) -> dict:
+    """``laa_clusters``' result -> entries of the metrics dict, keyed like ``densitometry_metrics`` (``names[label]`` of
+    a mapping or sequence, else the label as a string), for t = |threshold|: 'laa{t}_clusters_per_region' ("{:d}"),
+    'laa{t}_largest_cluster_ml_per_region' and 'laa{t}_cluster_d_per_region' ("{:.3f}", None -- json null -- for NaN),
+    their whole-lung twins ending '_per_lung' (one value each) and 'laa_cluster_connectivity' ("{:d}").  Row 0 is not
+    reported as a region.  Pure host code."""
+    def lst(v):
+        return v.tolist() if hasattr(v, "tolist") else v          # tensors, arrays and their scalars
+
+    def fmt(v, spec, cast=float):
+        if v is None or (isinstance(v, float) and math.isnan(v)):
+            return None
+        s = spec.format(cast(v))
+        return s.lstrip("-") if float(s) == 0 else s              # "-0.000" (a slope of +-1e-17) reads as 0.000
+
+    t = abs(int(result["threshold"]))
+    lung = result["whole_lung"]
+    cols = [(f"laa{t}_clusters", "clusters", "{:d}", int), (f"laa{t}_largest_cluster_ml", "largest_ml", "{:.3f}", float),
+            (f"laa{t}_cluster_d", "d", "{:.3f}", float)]
+    out = {}
+    for stem, field, spec, cast in cols:
+        per_row = lst(result[field])
+        if len(per_row) < 2:
+            raise ValueError("laa_cluster_metrics: the result must hold rows 0..n_regions")
+        d = {}
+        for label in range(1, len(per_row)):
+            try:
+                key = str(names[label]) if names is not None else str(label)
+            except (KeyError, IndexError):
+                key = str(label)
+            d[key] = fmt(per_row[label], spec, cast)
+        out[f"{stem}_per_region"] = d
+    for stem, field, spec, cast in cols:
+        out[f"{stem}_per_lung"] = fmt(lst(lung[field]), spec, cast)
+    out["laa_cluster_connectivity"] = "{:d}".format(int(result["connectivity"]))
+    return out
+
+
 def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=None) -> List[dict]:
     """processor.py:102-145 for a list of predict_step outputs: per scan the pasted CLE / PSE volumes (uint8 like
     the written .mha, and/or float) and the metrics entry of the results json.  A prediction that carries a
@@ -313,7 +411,7 @@ def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=No
 def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[float], target_size: Sequence[int],
                  uid=None, want_u8: bool = True, regions: bool = False, region_names=None, densitometry: bool = False,
                  densitometry_kw: Optional[dict] = None, core_peel: bool = False, peel_mm: float = 10.0,
-                 **prepare_kw) -> dict:
+                 clusters: bool = False, cluster_kw: Optional[dict] = None, **prepare_kw) -> dict:
     """One scan + its lobe segmentation -> its entry of ``build_outputs``: ``transforms.prepare_case`` (dataset.py:57-92)
     -> ``transforms.prepare_sample(target_size)`` -> a batch of one -> ``module.predict_step`` -> ``build_outputs``.
     The composition only; `prepare_kw` goes to ``prepare_case`` (crop_border, dilate_iterations, ...).  ``regions``:
@@ -330,10 +428,17 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     Network side: the composite zone labels travel as the batch's 'lobe_labels' with 'n_regions' = 2n, the one fused
     tail gives a [2n+1, 4] table, and the entry carries ``zone_region_metrics`` of it; with ``regions`` the table
     ``region_metrics`` reads is that one folded on the host (``fold_zone_table``).  A line in error_messages when lung
-    voxels carry a label above n_regions.  'full_cle' / 'full_pse' are the same bit for bit under every combination."""
-    want_lobes = bool(regions) or bool(densitometry) or bool(core_peel)
+    voxels carry a label above n_regions.
+
+    ``clusters`` (independent of the three): the entry also carries ``laa_cluster_metrics`` of ``laa_clusters`` on the
+    case's 'image' and 'lobe_labels' before the resize (``cluster_kw``: n_regions, threshold, connectivity), keyed
+    through ``region_names``, and a line in error_messages when LAA voxels carry a label above n_regions.
+    'full_cle' / 'full_pse' are the same bit for bit under every combination."""
+    want_lobes = bool(regions) or bool(densitometry) or bool(core_peel) or bool(clusters)
     case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=want_lobes, **prepare_kw)
-    dens = cp = None
+    dens = cp = clu = None
+    if clusters:
+        clu = laa_clusters(case["image"], case["lobe_labels"], spacing, **(cluster_kw or {}))
     if densitometry:
         dens = _densitometry(case["image"], case["lobe_labels"], spacing, **(densitometry_kw or {}))
     if core_peel:
@@ -375,16 +480,23 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
         if outside > 0:
             entry["error_messages"].append("{:d} lung voxels carry a lobe label outside 1..{:d}: they are in no region's "
                                            "peel or core".format(outside, cp["n_regions"]))
+    if clu is not None:
+        entry["metrics"].update(laa_cluster_metrics(clu, region_names))
+        outside = int(clu["voxels"][0])
+        if outside > 0:
+            entry["error_messages"].append("{:d} low-attenuation voxels carry a lobe label outside 1..{:d}: their "
+                                           "clusters are in no region".format(outside, clu["voxels"].shape[0] - 1))
     return entry
 
 
 def write_reports(results: List[dict], centrilobular_json: Optional[str] = None, paraseptal_json: Optional[str] = None,
                   output_json: Optional[str] = None, regions_json: Optional[str] = None,
-                  densitometry_json: Optional[str] = None, core_peel_json: Optional[str] = None):
+                  densitometry_json: Optional[str] = None, core_peel_json: Optional[str] = None,
+                  clusters_json: Optional[str] = None):
     """processor.py:160-177: the two single-scan score files and the results list; ``regions_json``: the regional
     entries (``REGION_KEYS``) of the first result, which must carry them; ``densitometry_json``: its densitometry
     entries (``densitometry_metrics``), likewise; ``core_peel_json``: its ``core_peel_metrics`` and
-    ``zone_region_metrics`` entries, likewise."""
+    ``zone_region_metrics`` entries, likewise; ``clusters_json``: its ``laa_cluster_metrics`` entries, likewise."""
     m = results[0]["metrics"]
     if centrilobular_json:
         with open(centrilobular_json, "w") as f:
@@ -415,4 +527,11 @@ def write_reports(results: List[dict], centrilobular_json: Optional[str] = None,
             raise ValueError("write_reports: core_peel_json needs a result with core / peel metrics "
                              "(predict_case(core_peel=True))")
         with open(core_peel_json, "w") as f:
+            f.write(json.dumps({k: m[k] for k in keys}))
+    if clusters_json:
+        keys = [k for k in m if _CLUSTER_KEY.fullmatch(k)]
+        if "laa_cluster_connectivity" not in keys or not any(k.endswith("_clusters_per_region") for k in keys):
+            raise ValueError("write_reports: clusters_json needs a result with cluster metrics "
+                             "(predict_case(clusters=True))")
+        with open(clusters_json, "w") as f:
             f.write(json.dumps({k: m[k] for k in keys}))

@@ -715,6 +715,34 @@ int dram_lung_zones(const void* labels, int label_dtype, long long stride_z, lon
                     uint8_t* zone_labels, float* dist_mm, void* workspace, int D, int H, int W, int sz_um, int sy_um,
                     int sx_um, long long peel_um, long long max_um, int n_regions, dram_stream_t stream);
 
+/* Connected-component labelling of a 3-D key volume and the per-row cluster table of the LAA cluster analysis
+ * (csrc/ccl.hip; definitions: INTEGRATION.md B8).  A key is a non-negative integer per voxel, 0 is background; two
+ * voxels are connected when they are neighbours under `connectivity` (6: faces; 26: faces, edges, corners) and carry the
+ * same non-zero key.  key_or_labels [D,H,W] of lab_elem 1 (uint8) or 2 (int16) bytes per element, read in place through
+ * stride_z / stride_y (in elements, >= 0; x stride 1) like dram_lobe_hist's labels.
+ *   image == NULL: the first argument is the key itself (a value <= 0 is background; threshold, by_lobe are ignored);
+ *   image [D,H,W] int16 HU, contiguous: the first argument holds lobe labels and the key is the LAA key: label > 0 and
+ *     hu < threshold (strict, as dram_lobe_hist's counts below a threshold) -> the label (by_lobe != 0) or 1.
+ *   components [D,H,W] int32: the linear index (z*H + y)*W + x of the smallest voxel of the voxel's component, -1 on
+ *     background (canonical: independent of scheduling);
+ *   cluster_voxels [D,H,W] int32, optional (NULL): the size of the voxel's component, 0 on background;
+ *   table [n_regions + 1][35] int64, a component in the row of its key (key r in 1..n_regions -> row r, a key above
+ *     n_regions -> row 0): columns 0..31 the components with 2^k <= size < 2^(k+1), 32 the number of components, 33 the
+ *     number of foreground voxels, 34 the largest size (0 for an empty row);
+ *   work: dram_label_components_workspace(D, H, W) bytes (int32 sizes + int16 key per voxel, each rounded up to 256
+ *     bytes; 0 for sizes the call refuses), 256-byte aligned, owned by the caller; needs no clearing.
+ * Four launches (init, merge, compress, table) and a fifth with cluster_voxels; every output element is written.
+ * Lock-free union-find: integer atomics only, no waiting between threads or workgroups, never synchronises,
+ * capturable; bit-identical from call to call.
+ * Null key_or_labels / components / table / work, lab_elem not 1 / 2, a size < 1, a negative stride, connectivity not
+ * 6 / 26, n_regions outside 1..15, threshold outside -32768..32768: DRAM_ERR_BAD_ARG.  D*H*W >= 2^31:
+ * DRAM_ERR_UNSUPPORTED. */
+size_t dram_label_components_workspace(int D, int H, int W);
+int dram_label_components(const void* key_or_labels, int lab_elem, long long stride_z, long long stride_y,
+                          const int16_t* image, int threshold, int by_lobe, int connectivity, int n_regions,
+                          int32_t* components, int32_t* cluster_voxels, int64_t* table, void* work, int D, int H, int W,
+                          dram_stream_t stream);
+
 /* Train-time augmentations (models.py:66-74) with GIVEN parameters, fused into one gather pass:
  * GaussianAddictive (intensity_transforms.py:145-177; noise [D,H,W] supplied by the caller, minmax[2] = volume
  * {min, max} on the device, e.g. folded from dram_minmax partials [nblk][2]), BoxMaskOut (:180-237), Flip
