@@ -124,6 +124,37 @@ def _req(t: Tensor, name: str, dtype=torch.float32, shape=None):
     return t
 
 
+def _n_regions(fn: str, n_regions, hi: int = 15) -> int:
+    """n_regions as an int in 1..hi: 15 rows are what the region kernels hold, 7 what ``lung_zones`` can still double."""
+    n = int(n_regions)
+    if not 1 <= n <= hi:
+        note = " (2 n <= 15 rows downstream)" if hi == 7 else ""
+        raise ValueError(f"{fn}: n_regions must be 1..{hi}{note}, got {n_regions}")
+    return n
+
+
+def _label_view(fn: str, t, name: str, like_shape=None):
+    """The label-volume operand of ``fn``, as the kernels read it in place: a non-empty [D,H,W] tensor of uint8 / int16
+    / bool (seen as uint8), of ``like_shape`` where given, below 2^31 voxels; a view whose x stride is not 1 is made
+    contiguous first.  -> (tensor, dtype code 1 | 2, z stride, y stride).  The host-only refusals come first; the one
+    device check (a CPU tensor ends there) is the last step."""
+    if not isinstance(t, Tensor) or t.dim() != 3 or min(t.shape) < 1:
+        raise ValueError(f"{fn}: {name} must be a non-empty [D,H,W] tensor")
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dtype not in (torch.uint8, torch.int16):
+        raise TypeError(f"{fn}: expected uint8, int16 or bool {name}, got {t.dtype}")
+    if like_shape is not None and tuple(t.shape) != tuple(like_shape):
+        raise ValueError(f"{fn}: {name} {tuple(t.shape)} must have the image's shape {tuple(like_shape)}")
+    if t.numel() >= 2 ** 31:
+        raise ValueError(f"{fn}: volumes of 2^31 voxels or more are not supported")
+    if (t.shape[2] > 1 and t.stride(2) != 1) or min(t.stride()) < 0:
+        t = t.contiguous()
+    with launch_scope(t.device):
+        _req(t[0, 0], f"{fn}: {name}", t.dtype)                    # device; a row is contiguous
+    return t, (2 if t.dtype == torch.int16 else 1), int(t.stride(0)), int(t.stride(1))
+
+
 BF16 = torch.bfloat16
 
 
@@ -1311,9 +1342,7 @@ def upproject_regions(cle: Tensor, pse: Tensor, ess_u8: Tensor, labels_u8: Tenso
     (None, None when ``want_volumes`` is off), and table [B, n_regions + 1, 4] float64, row r = (sum up_cle, sum up_pse,
     #(ess != 0), #voxels) over labels == r; row 0 also takes every label above n_regions.  Deterministic; every check
     runs before any launch."""
-    n = int(n_regions)
-    if not 1 <= n <= 15:
-        raise ValueError(f"upproject_regions: n_regions must be 1..15, got {n_regions}")
+    n = _n_regions("upproject_regions", n_regions)
     for t, name in ((cle, "cle"), (pse, "pse")):
         if not isinstance(t, Tensor) or t.dim() != 4 or min(t.shape) < 1:
             raise ValueError(f"upproject_regions: {name} must be a non-empty [B,D,H,W] tensor")
@@ -1359,35 +1388,21 @@ def lobe_histogram(image: Tensor, labels: Tensor, n_regions: int = 5, hu_lo: int
     label <= 0 is counted nowhere, so the rows add up to ``labels > 0``.  Supported: nbins a multiple of 64 in 64..2048,
     (n_regions + 1) * nbins <= 32768, hu_lo .. hu_lo + nbins - 1 inside int16, fewer than 2^31 voxels.  Integer counts:
     bit-identical from call to call; never synchronises; every check runs before any launch."""
-    n, lo, nb = int(n_regions), int(hu_lo), int(nbins)
-    if not 1 <= n <= 15:
-        raise ValueError(f"lobe_histogram: n_regions must be 1..15, got {n_regions}")
-    for t, name in ((image, "image"), (labels, "labels")):
-        if not isinstance(t, Tensor) or t.dim() != 3 or min(t.shape) < 1:
-            raise ValueError(f"lobe_histogram: {name} must be a non-empty [D,H,W] tensor")
-    if labels.dtype == torch.bool:
-        labels = labels.view(torch.uint8)
-    if labels.dtype not in (torch.uint8, torch.int16):
-        raise TypeError(f"lobe_histogram: expected uint8, int16 or bool labels, got {labels.dtype}")
-    if tuple(labels.shape) != tuple(image.shape):
-        raise ValueError(f"lobe_histogram: labels {tuple(labels.shape)} must have the image's shape {tuple(image.shape)}")
+    n, lo, nb = _n_regions("lobe_histogram", n_regions), int(hu_lo), int(nbins)
+    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
+        raise ValueError("lobe_histogram: image must be a non-empty [D,H,W] tensor")
+    labels, code, sz, sy = _label_view("lobe_histogram", labels, "labels", image.shape)
     D, H, W = (int(v) for v in image.shape)
-    if D * H * W >= 2 ** 31:
-        raise ValueError("lobe_histogram: volumes of 2^31 voxels or more are not supported")
-    if (W > 1 and labels.stride(2) != 1) or min(labels.stride()) < 0:
-        labels = labels.contiguous()
-    dev = image.device
+    dev = labels.device
     with launch_scope(dev):
         _req(image, "lobe_histogram: image", torch.int16)
-        _req(labels[0, 0], "lobe_histogram: labels", labels.dtype)       # device; a row is contiguous
         nblk = _L().dram_lobe_hist_nblk(D * H * W)
         part_hist = torch.empty((nblk, n + 1, nb), device=dev, dtype=torch.int32)
         part_sums = torch.empty((nblk, n + 1, 2), device=dev, dtype=torch.int64)
         hist = torch.empty((n + 1, nb), device=dev, dtype=torch.int64)
         sums = torch.empty((n + 1, 2), device=dev, dtype=torch.int64)
-        _chk(_L().dram_lobe_hist(_p(image), _p(labels), 2 if labels.dtype == torch.int16 else 1, int(labels.stride(0)),
-                                 int(labels.stride(1)), _p(part_hist), _p(part_sums), _p(hist), _p(sums), D, H, W, n, lo,
-                                 nb, _stream()), "dram_lobe_hist")
+        _chk(_L().dram_lobe_hist(_p(image), _p(labels), code, sz, sy, _p(part_hist), _p(part_sums), _p(hist), _p(sums),
+                                 D, H, W, n, lo, nb, _stream()), "dram_lobe_hist")
     return hist, sums
 
 
@@ -1436,70 +1451,39 @@ def lung_zones(labels: Tensor, spacing, peel_mm: float, n_regions: Optional[int]
       dist_mm float32 (``want_dist``): sqrt(d2) / 1000, 0 outside the lung, +inf where d2 is.
     Supported: fewer than 2^31 voxels, spacing 1..20000 um and (size - 1) * spacing < 2^25 um on every axis.  Exact
     integers: bit-identical from call to call; never synchronises; every check runs before any launch."""
-    if not isinstance(labels, Tensor) or labels.dim() != 3 or min(labels.shape) < 1:
-        raise ValueError("lung_zones: labels must be a non-empty [D,H,W] tensor")
-    if labels.dtype == torch.bool:
-        labels = labels.view(torch.uint8)
-    if labels.dtype not in (torch.uint8, torch.int16):
-        raise TypeError(f"lung_zones: expected uint8, int16 or bool labels, got {labels.dtype}")
     s_um, peel_um, max_um = lung_zones_units(spacing, peel_mm, max_mm)
-    n = 0
-    if n_regions is not None:
-        n = int(n_regions)
-        if not 1 <= n <= 7:
-            raise ValueError(f"lung_zones: n_regions must be 1..7 (2 n <= 15 rows downstream), got {n_regions}")
+    n = 0 if n_regions is None else _n_regions("lung_zones", n_regions, 7)
+    if isinstance(labels, Tensor) and labels.dim() == 3:               # anything else: _label_view's refusal below
+        for size, s, axis in zip(labels.shape, s_um, "zyx"):
+            if (size - 1) * s >= 2 ** 25:
+                raise ValueError(f"lung_zones: axis {axis}: (size - 1) * spacing = {(size - 1) * s} um must be below 2^25")
+    labels, code, sz, sy = _label_view("lung_zones", labels, "labels")
     D, H, W = (int(v) for v in labels.shape)
-    if D * H * W >= 2 ** 31:
-        raise ValueError("lung_zones: volumes of 2^31 voxels or more are not supported")
-    for size, s, axis in zip((D, H, W), s_um, "zyx"):
-        if (size - 1) * s >= 2 ** 25:
-            raise ValueError(f"lung_zones: axis {axis}: (size - 1) * spacing = {(size - 1) * s} um must be below 2^25")
-    if (W > 1 and labels.stride(2) != 1) or min(labels.stride()) < 0:
-        labels = labels.contiguous()
     dev = labels.device
     with launch_scope(dev):
-        _req(labels[0, 0], "lung_zones: labels", labels.dtype)           # device; a row is contiguous
         nbytes = int(_L().dram_lung_zones_workspace(D, H, W, max_um))
         work = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
         zones = torch.empty((D, H, W), device=dev, dtype=torch.uint8)
         zlab = torch.empty((D, H, W), device=dev, dtype=torch.uint8) if n else None
         dist = torch.empty((D, H, W), device=dev, dtype=torch.float32) if want_dist else None
-        _chk(_L().dram_lung_zones(_p(labels), 2 if labels.dtype == torch.int16 else 1, int(labels.stride(0)),
-                                  int(labels.stride(1)), _p(zones), _p(zlab), _p(dist), _p(work), D, H, W, *s_um, peel_um,
-                                  max_um, n, _stream()), "dram_lung_zones")
+        _chk(_L().dram_lung_zones(_p(labels), code, sz, sy, _p(zones), _p(zlab), _p(dist), _p(work), D, H, W, *s_um,
+                                  peel_um, max_um, n, _stream()), "dram_lung_zones")
     return zones, zlab, dist
 
 
 CCL_TABLE_COLS = 35             # 32 size bins (2^k <= size < 2^(k+1)), components, foreground voxels, largest size
 
 
-def _label_volume(t, fn: str, name: str) -> Tensor:
-    """A key / label operand of the component labelling: a non-empty [D,H,W] tensor of bool / uint8 / int16, bool seen
-    as uint8.  Type and shape only: nothing here touches the device."""
-    if not isinstance(t, Tensor) or t.dim() != 3 or min(t.shape) < 1:
-        raise ValueError(f"{fn}: {name} must be a non-empty [D,H,W] tensor")
-    if t.dtype == torch.bool:
-        t = t.view(torch.uint8)
-    if t.dtype not in (torch.uint8, torch.int16):
-        raise TypeError(f"{fn}: expected uint8, int16 or bool {name}, got {t.dtype}")
-    return t
-
-
-def _label_components(fn: str, labels: Tensor, image: Optional[Tensor], threshold: int, by_lobe: bool, connectivity: int,
-                      n_regions: int, want_sizes: bool):
-    n, conn = int(n_regions), int(connectivity)
+def _label_components(fn: str, name: str, labels: Tensor, image: Optional[Tensor], threshold: int, by_lobe: bool,
+                      connectivity: int, n_regions: int, want_sizes: bool):
+    conn = int(connectivity)
     if conn not in (6, 26):
         raise ValueError(f"{fn}: connectivity must be 6 or 26, got {connectivity}")
-    if not 1 <= n <= 15:
-        raise ValueError(f"{fn}: n_regions must be 1..15, got {n_regions}")
+    n = _n_regions(fn, n_regions)
+    labels, code, sz, sy = _label_view(fn, labels, name, None if image is None else image.shape)
     D, H, W = (int(v) for v in labels.shape)
-    if D * H * W >= 2 ** 31:
-        raise ValueError(f"{fn}: volumes of 2^31 voxels or more are not supported")
-    if (W > 1 and labels.stride(2) != 1) or min(labels.stride()) < 0:
-        labels = labels.contiguous()
     dev = labels.device
     with launch_scope(dev):
-        _req(labels[0, 0], f"{fn}: {'labels' if image is not None else 'key'}", labels.dtype)   # a row is contiguous
         if image is not None:
             _req(image, f"{fn}: image", torch.int16)
         nbytes = int(_L().dram_label_components_workspace(D, H, W))
@@ -1507,8 +1491,7 @@ def _label_components(fn: str, labels: Tensor, image: Optional[Tensor], threshol
         comp = torch.empty((D, H, W), device=dev, dtype=torch.int32)
         sizes = torch.empty((D, H, W), device=dev, dtype=torch.int32) if want_sizes else None
         table = torch.empty((n + 1, CCL_TABLE_COLS), device=dev, dtype=torch.int64)
-        _chk(_L().dram_label_components(_p(labels), 2 if labels.dtype == torch.int16 else 1, int(labels.stride(0)),
-                                        int(labels.stride(1)), _p(image), int(threshold), 1 if by_lobe else 0, conn, n,
+        _chk(_L().dram_label_components(_p(labels), code, sz, sy, _p(image), int(threshold), 1 if by_lobe else 0, conn, n,
                                         _p(comp), _p(sizes), _p(table), _p(work), D, H, W, _stream()),
              "dram_label_components")
     return comp, table, sizes
@@ -1528,8 +1511,7 @@ def label_components(key: Tensor, connectivity: int = 6, n_regions: int = 5, wan
       cluster_voxels int32 [D,H,W] (``want_sizes``): the size of the voxel's component, 0 on background.
     Fewer than 2^31 voxels.  Integer atomics only: bit-identical from call to call; never synchronises; every check runs
     before any launch."""
-    key = _label_volume(key, "label_components", "key")
-    return _label_components("label_components", key, None, 0, True, connectivity, n_regions, want_sizes)
+    return _label_components("label_components", "key", key, None, 0, True, connectivity, n_regions, want_sizes)
 
 
 def laa_components(image: Tensor, labels: Tensor, threshold: int = -950, n_regions: int = 5, connectivity: int = 6,
@@ -1541,17 +1523,14 @@ def laa_components(image: Tensor, labels: Tensor, threshold: int = -950, n_regio
     of ``densitometry``'s 'laa_counts'), else 0 -- clusters do not cross a fissure, each belongs to one lobe -- or, with
     ``by_lobe=False``, 1 there: whole-lung clusters, reported in row 1 of a table of two rows.  threshold: an integer HU
     in -32768..32768.  -> the triple of ``label_components``."""
-    labels = _label_volume(labels, "laa_components", "labels")
     if not isinstance(image, Tensor) or image.dim() != 3:
         raise ValueError("laa_components: image must be a [D,H,W] tensor")
     if image.dtype != torch.int16:
         raise TypeError(f"laa_components: expected an int16 image, got {image.dtype}")
-    if tuple(labels.shape) != tuple(image.shape):
-        raise ValueError(f"laa_components: labels {tuple(labels.shape)} must have the image's shape {tuple(image.shape)}")
     t = int(threshold)
     if t != threshold or not -32768 <= t <= 32768:
         raise ValueError(f"laa_components: threshold must be an integer HU in -32768..32768, got {threshold}")
-    return _label_components("laa_components", labels, image, t, bool(by_lobe), connectivity,
+    return _label_components("laa_components", "labels", labels, image, t, bool(by_lobe), connectivity,
                              n_regions if by_lobe else 1, want_sizes)
 
 

@@ -15,7 +15,7 @@ if not __package__:          # imported top-level (this directory on sys.path): 
 import json
 import math
 import re
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -53,6 +53,42 @@ def resample_paste(dense: torch.Tensor, crop_slice, original_size: Sequence[int]
     return of, ob
 
 
+def _region_key(names, label: int) -> str:
+    """``names[label]`` (a mapping or a sequence indexed by the label) or else the label as a string, the form json
+    gives it: the key of one region in every per-region dict of the report."""
+    try:
+        return str(names[label]) if names is not None else str(label)
+    except (KeyError, IndexError):
+        return str(label)
+
+
+def _fmt(v, spec: str, cast=float, unsigned_zero: bool = False) -> Optional[str]:
+    """One number of the report: None (json null) for None or NaN, else ``spec.format(cast(v))``; ``unsigned_zero``: a
+    value that prints as zero prints without a sign ("-0.000" reads "0.000")."""
+    if v is None or (isinstance(v, float) and math.isnan(v)):
+        return None
+    s = spec.format(cast(v))
+    return s.lstrip("-") if unsigned_zero and float(s) == 0 else s
+
+
+def _lst(v):
+    return v.tolist() if hasattr(v, "tolist") else v              # tensors, arrays and their scalars
+
+
+def _column_metrics(caller: str, cols, names=None, unsigned_zero: bool = False) -> dict:
+    """cols [(stem, values of the rows 0..n_regions, whole-lung value, spec, cast)] -> every '{stem}_per_region' dict
+    (rows 1..n, keyed through ``names``), then every '{stem}_per_lung' value, all through ``_fmt``."""
+    out = {}
+    for stem, per_row, _, spec, cast in cols:
+        if len(per_row) < 2:
+            raise ValueError(f"{caller}: the result must hold rows 0..n_regions")
+        out[f"{stem}_per_region"] = {_region_key(names, label): _fmt(per_row[label], spec, cast, unsigned_zero)
+                                     for label in range(1, len(per_row))}
+    for stem, _, whole, spec, cast in cols:
+        out[f"{stem}_per_lung"] = _fmt(whole, spec, cast, unsigned_zero)
+    return out
+
+
 REGION_KEYS = ("cle_lesion_percentage_per_region", "cle_severity_score_per_region", "pse_lesion_percentage_per_region",
                "pse_severity_score_per_region", "region_voxels", "region_ess_fraction")
 
@@ -69,10 +105,7 @@ def region_metrics(table_row, names=None) -> dict:
         raise ValueError("region_metrics: table_row must be [n_regions + 1, 4]")
     out = {k: {} for k in REGION_KEYS}
     for label in range(1, len(rows)):
-        try:
-            key = str(names[label]) if names is not None else str(label)
-        except (KeyError, IndexError):
-            key = str(label)
+        key = _region_key(names, label)
         s_cle, s_pse, n_ess, n_vox = (float(v) for v in rows[label])
         present = n_vox > 0
         for head, s, rmap in (("cle", s_cle, CLE_RATIO_MAP), ("pse", s_pse, PSE_RATIO_MAP)):
@@ -148,42 +181,20 @@ def densitometry(image: torch.Tensor, labels: torch.Tensor, spacing: Sequence[fl
     return densitometry_from_hist(hist, sums, spacing, thresholds, percentiles, hu_lo)
 
 
-_densitometry = densitometry         # predict_case's switch has the function's name
-
-
 def densitometry_metrics(result: dict, names=None) -> dict:
     """``densitometry``'s result -> entries of the metrics dict, beside ``region_metrics`` and keyed like it
     (``names[label]`` of a mapping or sequence, else the label as a string): 'laa{|t|}_fraction_per_region' per
     threshold and 'mean_lung_density_per_region' ("{:.3f}"), 'perc{p}_hu_per_region' ("{:d}"), 'volume_ml_per_region'
     ("{:.1f}"), and their whole-lung twins ending '_per_lung' (one value each).  None (json null) stands for NaN.
     Row 0 is not reported as a region.  Pure host code."""
-    def lst(v):
-        return v.tolist() if hasattr(v, "tolist") else v          # tensors, arrays and their scalars
-
-    def fmt(v, spec, cast=float):
-        return None if v is None or (isinstance(v, float) and math.isnan(v)) else spec.format(cast(v))
-
     ts, ps = list(result["thresholds"]), list(result["percentiles"])
     lung = result["whole_lung"]
-    cols = [(f"laa{abs(t)}_fraction", lst(result["laa"])[i], lst(lung["laa"])[i], "{:.3f}", float) for i, t in enumerate(ts)]
-    cols += [(f"perc{p}_hu", lst(result["perc"])[i], lst(lung["perc"])[i], "{:d}", int) for i, p in enumerate(ps)]
-    cols += [("mean_lung_density", lst(result["mean_density"]), lst(lung["mean_density"]), "{:.3f}", float),
-             ("volume_ml", lst(result["volume_ml"]), lst(lung["volume_ml"]), "{:.1f}", float)]
-    out = {}
-    for stem, per_row, whole, spec, cast in cols:
-        if len(per_row) < 2:
-            raise ValueError("densitometry_metrics: the result must hold rows 0..n_regions")
-        d = {}
-        for label in range(1, len(per_row)):
-            try:
-                key = str(names[label]) if names is not None else str(label)
-            except (KeyError, IndexError):
-                key = str(label)
-            d[key] = fmt(per_row[label], spec, cast)
-        out[f"{stem}_per_region"] = d
-    for stem, per_row, whole, spec, cast in cols:
-        out[f"{stem}_per_lung"] = fmt(whole, spec, cast)
-    return out
+    laa, perc, lung_laa, lung_perc = (_lst(v) for v in (result["laa"], result["perc"], lung["laa"], lung["perc"]))
+    cols = [(f"laa{abs(t)}_fraction", laa[i], lung_laa[i], "{:.3f}", float) for i, t in enumerate(ts)]
+    cols += [(f"perc{p}_hu", perc[i], lung_perc[i], "{:d}", int) for i, p in enumerate(ps)]
+    cols += [("mean_lung_density", _lst(result["mean_density"]), _lst(lung["mean_density"]), "{:.3f}", float),
+             ("volume_ml", _lst(result["volume_ml"]), _lst(lung["volume_ml"]), "{:.1f}", float)]
+    return _column_metrics("densitometry_metrics", cols, names)        # a mean of -0.0004 keeps its sign: "-0.000"
 
 
 # --------------------------------------------------------------------------- core / peel split of the per-lobe report
@@ -218,9 +229,6 @@ def core_peel(image: torch.Tensor, labels: torch.Tensor, spacing: Sequence[float
                                            torch.cat([torch.zeros_like(sums[:1]), sums[rows]]), spacing, hu_lo=hu_lo, **kw)
     out.update(outside_voxels=sums[0, 0], zones=zones, zone_labels=zone_labels, peel_mm=float(peel_mm), n_regions=n)
     return out
-
-
-_core_peel = core_peel               # predict_case's switch has the function's name
 
 
 def core_peel_metrics(result: dict, names=None) -> dict:
@@ -261,10 +269,7 @@ def zone_region_metrics(table_row, names=None) -> dict:
         per[f"region_voxels_{zone}"] = {}
         tot = [0.0, 0.0, 0.0]
         for label in range(1, n + 1):
-            try:
-                key = str(names[label]) if names is not None else str(label)
-            except (KeyError, IndexError):
-                key = str(label)
+            key = _region_key(names, label)
             s_cle, s_pse, _, n_vox = (float(v) for v in rows[i * n + label])
             for h, s in (("cle", s_cle), ("pse", s_pse)):
                 per[f"{h}_lesion_percentage_per_region_{zone}"][key] = "{:.3f}".format(s / n_vox) if n_vox > 0 else None
@@ -342,36 +347,52 @@ def laa_cluster_metrics(result: dict, names=None) -> dict:
     'laa{t}_largest_cluster_ml_per_region' and 'laa{t}_cluster_d_per_region' ("{:.3f}", None -- json null -- for NaN),
     their whole-lung twins ending '_per_lung' (one value each) and 'laa_cluster_connectivity' ("{:d}").  Row 0 is not
     reported as a region.  Pure host code."""
-    def lst(v):
-        return v.tolist() if hasattr(v, "tolist") else v          # tensors, arrays and their scalars
-
-    def fmt(v, spec, cast=float):
-        if v is None or (isinstance(v, float) and math.isnan(v)):
-            return None
-        s = spec.format(cast(v))
-        return s.lstrip("-") if float(s) == 0 else s              # "-0.000" (a slope of +-1e-17) reads as 0.000
-
     t = abs(int(result["threshold"]))
     lung = result["whole_lung"]
-    cols = [(f"laa{t}_clusters", "clusters", "{:d}", int), (f"laa{t}_largest_cluster_ml", "largest_ml", "{:.3f}", float),
-            (f"laa{t}_cluster_d", "d", "{:.3f}", float)]
-    out = {}
-    for stem, field, spec, cast in cols:
-        per_row = lst(result[field])
-        if len(per_row) < 2:
-            raise ValueError("laa_cluster_metrics: the result must hold rows 0..n_regions")
-        d = {}
-        for label in range(1, len(per_row)):
-            try:
-                key = str(names[label]) if names is not None else str(label)
-            except (KeyError, IndexError):
-                key = str(label)
-            d[key] = fmt(per_row[label], spec, cast)
-        out[f"{stem}_per_region"] = d
-    for stem, field, spec, cast in cols:
-        out[f"{stem}_per_lung"] = fmt(lst(lung[field]), spec, cast)
+    cols = [(f"laa{t}_{stem}", _lst(result[field]), _lst(lung[field]), spec, cast) for stem, field, spec, cast in
+            (("clusters", "clusters", "{:d}", int), ("largest_cluster_ml", "largest_ml", "{:.3f}", float),
+             ("cluster_d", "d", "{:.3f}", float))]
+    out = _column_metrics("laa_cluster_metrics", cols, names, unsigned_zero=True)   # a slope of +-1e-17 reads 0.000
     out["laa_cluster_connectivity"] = "{:d}".format(int(result["connectivity"]))
     return out
+
+
+# --------------------------------------------------------------------------- the sections of the report
+class _Section(NamedTuple):
+    """One optional section of the predict report; ``_SECTIONS`` maps ``predict_case``'s switch to it.  Adding an analysis
+    to the report is one record there (plus its switch and its json argument in the two signatures)."""
+    json_arg: str                                   # write_reports' argument for the section's own file
+    select: Union[Tuple[str, ...], re.Pattern]      # the section's metric keys: the names, or a pattern they match in full
+    required: Tuple[str, ...]                       # patterns that selected keys must match, or the section is absent
+    hint: str                                       # what write_reports says is missing
+    # the scan side, run on the prepared case before the resize (None: the section comes from predict_step's table)
+    run: Optional[Callable] = None                  # (image, lobe_labels, spacing, **kw) -> result; device work only
+    metrics: Optional[Callable] = None              # (result, region_names) -> metrics entries
+    outside: Optional[Callable] = None              # result -> (voxels outside 1..n, n); reads the device
+    error: str = ""                                 # the error_messages line, .format(outside, n)
+
+
+def _row0_voxels(result):
+    return int(result["voxels"][0]), result["voxels"].shape[0] - 1
+
+
+_SECTIONS = {          # in the order of the report: metric keys, error lines and files follow it
+    "regions": _Section("regions_json", REGION_KEYS, REGION_KEYS, "regional metrics"),
+    "densitometry": _Section(
+        "densitometry_json", _DENSITO_KEY, ("mean_lung_density_per_region",), "densitometry metrics",
+        densitometry, densitometry_metrics, _row0_voxels,
+        "{:d} lung voxels carry a lobe label outside 1..{:d}: their density is in no region"),
+    "core_peel": _Section(
+        "core_peel_json", _CORE_PEEL_KEY, ("mean_lung_density_per_region_peel", "region_voxels_peel", "peel_mm"),
+        "core / peel metrics", core_peel, lambda r, names: {**core_peel_metrics(r, names), **r["zone_metrics"]},
+        lambda r: (int(r["outside_voxels"]), r["n_regions"]),
+        "{:d} lung voxels carry a lobe label outside 1..{:d}: they are in no region's peel or core"),
+    "clusters": _Section(
+        "clusters_json", _CLUSTER_KEY, ("laa_cluster_connectivity", r"laa\d+_clusters_per_region"), "cluster metrics",
+        laa_clusters, laa_cluster_metrics, _row0_voxels,
+        "{:d} low-attenuation voxels carry a lobe label outside 1..{:d}: their clusters are in no region"),
+}
+_LAUNCH_ORDER = ("clusters", "densitometry", "core_peel")          # the order the scan-side kernels are issued in
 
 
 def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=None) -> List[dict]:
@@ -434,20 +455,21 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     case's 'image' and 'lobe_labels' before the resize (``cluster_kw``: n_regions, threshold, connectivity), keyed
     through ``region_names``, and a line in error_messages when LAA voxels carry a label above n_regions.
     'full_cle' / 'full_pse' are the same bit for bit under every combination."""
-    want_lobes = bool(regions) or bool(densitometry) or bool(core_peel) or bool(clusters)
-    case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=want_lobes, **prepare_kw)
-    dens = cp = clu = None
-    if clusters:
-        clu = laa_clusters(case["image"], case["lobe_labels"], spacing, **(cluster_kw or {}))
-    if densitometry:
-        dens = _densitometry(case["image"], case["lobe_labels"], spacing, **(densitometry_kw or {}))
+    on = {"regions": bool(regions), "densitometry": bool(densitometry), "core_peel": bool(core_peel),
+          "clusters": bool(clusters)}
+    kw = {"densitometry": dict(densitometry_kw or {}), "clusters": dict(cluster_kw or {})}
     if core_peel:
         n = int(getattr(module.args, "n_regions", 5))
-        kw = dict(densitometry_kw or {})
-        if int(kw.pop("n_regions", n)) != n:
+        kw["core_peel"] = dict(densitometry_kw or {}, peel_mm=peel_mm)
+        if int(kw["core_peel"].setdefault("n_regions", n)) != n:
             raise ValueError(f"predict_case: core_peel splits the module's n_regions = {n} lobes; densitometry_kw asks "
                              "for another count")
-        cp = _core_peel(case["image"], case["lobe_labels"], spacing, peel_mm, n, **kw)
+    case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=any(on.values()), **prepare_kw)
+    results = {name: _SECTIONS[name].run(case["image"], case["lobe_labels"], spacing, **kw[name])
+               for name in _LAUNCH_ORDER if on[name]}
+    cp = results.get("core_peel")
+    # core / peel rides the network side on the regions' tail: its zone labels are the batch's labels, with 2n regions
+    if cp is not None:
         case = dict(case, lobe_labels=cp["zone_labels"])
     elif not regions:
         case = {k: v for k, v in case.items() if k != "lobe_labels"}
@@ -456,36 +478,22 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     keys = ("image", "lung_mask", "ess_mask", "crop_slice", "original_size") + (("lobe_labels",) if labelled else ())
     batch = {k: sample[k].unsqueeze(0) for k in keys}
     batch["uid"] = [uid]
-    zone_metrics = None
     if cp is not None:
         batch["n_regions"] = 2 * cp["n_regions"]
     pred = module.predict_step(batch, 0)
     if cp is not None:
         composite = pred["region_table"][0].cpu()
-        zone_metrics = zone_region_metrics(composite, region_names)
+        results["core_peel"] = dict(cp, zone_metrics=zone_region_metrics(composite, region_names))
         pred = {k: v for k, v in pred.items() if k != "region_table"}
         if regions:
             pred["region_table"] = fold_zone_table(composite).unsqueeze(0)
     entry = build_outputs([pred], want_u8=want_u8, region_names=region_names)[0]
-    if dens is not None:
-        entry["metrics"].update(densitometry_metrics(dens, region_names))
-        outside = int(dens["voxels"][0])
-        if outside > 0:
-            entry["error_messages"].append("{:d} lung voxels carry a lobe label outside 1..{:d}: their density is in no "
-                                           "region".format(outside, dens["voxels"].shape[0] - 1))
-    if cp is not None:
-        entry["metrics"].update(core_peel_metrics(cp, region_names))
-        entry["metrics"].update(zone_metrics)
-        outside = int(cp["outside_voxels"])
-        if outside > 0:
-            entry["error_messages"].append("{:d} lung voxels carry a lobe label outside 1..{:d}: they are in no region's "
-                                           "peel or core".format(outside, cp["n_regions"]))
-    if clu is not None:
-        entry["metrics"].update(laa_cluster_metrics(clu, region_names))
-        outside = int(clu["voxels"][0])
-        if outside > 0:
-            entry["error_messages"].append("{:d} low-attenuation voxels carry a lobe label outside 1..{:d}: their "
-                                           "clusters are in no region".format(outside, clu["voxels"].shape[0] - 1))
+    for name, section in _SECTIONS.items():
+        if name in results:
+            entry["metrics"].update(section.metrics(results[name], region_names))
+            outside, n = section.outside(results[name])
+            if outside > 0:
+                entry["error_messages"].append(section.error.format(outside, n))
     return entry
 
 
@@ -509,29 +517,15 @@ def write_reports(results: List[dict], centrilobular_json: Optional[str] = None,
     if output_json:
         with open(output_json, "w") as f:
             f.write(json.dumps([{k: r[k] for k in ("entity", "metrics", "error_messages")} for r in results]))
-    if regions_json:
-        if any(k not in m for k in REGION_KEYS):
-            raise ValueError("write_reports: regions_json needs a result with regional metrics (predict_case(regions=True))")
-        with open(regions_json, "w") as f:
-            f.write(json.dumps({k: m[k] for k in REGION_KEYS}))
-    if densitometry_json:
-        keys = [k for k in m if _DENSITO_KEY.fullmatch(k)]
-        if "mean_lung_density_per_region" not in keys:
-            raise ValueError("write_reports: densitometry_json needs a result with densitometry metrics "
-                             "(predict_case(densitometry=True))")
-        with open(densitometry_json, "w") as f:
-            f.write(json.dumps({k: m[k] for k in keys}))
-    if core_peel_json:
-        keys = [k for k in m if _CORE_PEEL_KEY.fullmatch(k)]
-        if "mean_lung_density_per_region_peel" not in keys or "region_voxels_peel" not in keys or "peel_mm" not in keys:
-            raise ValueError("write_reports: core_peel_json needs a result with core / peel metrics "
-                             "(predict_case(core_peel=True))")
-        with open(core_peel_json, "w") as f:
-            f.write(json.dumps({k: m[k] for k in keys}))
-    if clusters_json:
-        keys = [k for k in m if _CLUSTER_KEY.fullmatch(k)]
-        if "laa_cluster_connectivity" not in keys or not any(k.endswith("_clusters_per_region") for k in keys):
-            raise ValueError("write_reports: clusters_json needs a result with cluster metrics "
-                             "(predict_case(clusters=True))")
-        with open(clusters_json, "w") as f:
+    paths = {"regions_json": regions_json, "densitometry_json": densitometry_json, "core_peel_json": core_peel_json,
+             "clusters_json": clusters_json}
+    for name, section in _SECTIONS.items():
+        if not paths[section.json_arg]:
+            continue
+        sel = section.select
+        keys = [k for k in sel if k in m] if isinstance(sel, tuple) else [k for k in m if sel.fullmatch(k)]
+        if not all(any(re.fullmatch(need, k) for k in keys) for need in section.required):
+            raise ValueError(f"write_reports: {section.json_arg} needs a result with {section.hint} "
+                             f"(predict_case({name}=True))")
+        with open(paths[section.json_arg], "w") as f:
             f.write(json.dumps({k: m[k] for k in keys}))

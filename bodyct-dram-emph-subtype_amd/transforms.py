@@ -75,24 +75,16 @@ def prepare_labels(labels: torch.Tensor, target_size: Sequence[int]) -> torch.Te
     """labels [D,H,W] uint8 / int16 / bool (a view with unit x stride is read in place, e.g. the lung crop of the lobe
     volume) -> uint8 [Do,Ho,Wo]: ``prepare_mask``'s nearest rule, values clamped to 0..255.  The source is neither
     copied nor converted to float; ``prepare_labels(l) > 0`` equals ``prepare_mask(l > 0)`` voxel for voxel."""
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or min(labels.shape) < 1:
-        raise ValueError("prepare_labels: labels must be a non-empty [D,H,W] tensor")
-    if labels.dtype == torch.bool:
-        labels = labels.view(torch.uint8)
-    if labels.dtype not in (torch.uint8, torch.int16):
-        raise TypeError(f"prepare_labels: expected uint8, int16 or bool labels, got {labels.dtype}")
+    labels, code, sz, sy = ops._label_view("prepare_labels", labels, "labels")
     D, H, W = (int(v) for v in labels.shape)
-    if (W > 1 and labels.stride(2) != 1) or min(labels.stride()) < 0:
-        labels = labels.contiguous()
-    _req(labels[0, 0], "labels", labels.dtype)                   # device; a row is contiguous
     Do, Ho, Wo = (int(v) for v in target_size)
     if min(Do, Ho, Wo) < 1:
         raise ValueError(f"prepare_labels: target_size {(Do, Ho, Wo)} must be positive")
-    zidx = depth_indices(D, Do, labels.device)
-    out = torch.empty((Do, Ho, Wo), device=labels.device, dtype=torch.uint8)
-    _chk(_L().dram_prep_labels(_p(labels), 2 if labels.dtype == torch.int16 else 1, int(labels.stride(0)),
-                               int(labels.stride(1)), _p(zidx), _p(out), D, H, W, Do, Ho, Wo, _stream()),
-         "dram_prep_labels")
+    with ops.launch_scope(labels.device):
+        zidx = depth_indices(D, Do, labels.device)
+        out = torch.empty((Do, Ho, Wo), device=labels.device, dtype=torch.uint8)
+        _chk(_L().dram_prep_labels(_p(labels), code, sz, sy, _p(zidx), _p(out), D, H, W, Do, Ho, Wo, _stream()),
+             "dram_prep_labels")
     return out
 
 
