@@ -1534,6 +1534,54 @@ def laa_components(image: Tensor, labels: Tensor, threshold: int = -950, n_regio
                              n_regions if by_lobe else 1, want_sizes)
 
 
+def median_size(fn: str, size) -> Tuple[int, int, int]:
+    """A median window ``size`` -- three entries in (z, y, x) order, each 1 or 3, at least one 3 -- as a tuple of ints;
+    ValueError for anything else.  Pure host code."""
+    try:
+        s = tuple(size)
+    except TypeError:
+        s = ()
+    if len(s) != 3 or any(isinstance(v, bool) or v not in (1, 3) for v in s) or max(s) != 3:
+        raise ValueError(f"{fn}: size must have three entries (z, y, x), each 1 or 3 and at least one 3, got {size!r}")
+    return tuple(int(v) for v in s)
+
+
+def median_filter3d(image: Tensor, size=(3, 3, 3), out: Optional[Tensor] = None) -> Tensor:
+    """Median filter of a scan (csrc/median.hip; definitions: INTEGRATION.md B9): every voxel becomes the median of the
+    ``size`` window centred on it, indices clamped to the volume -- ``scipy.ndimage.median_filter(image, size,
+    mode='nearest')``, exactly.
+
+    image [D,H,W] int16 (made contiguous if it is not; never written); size (z, y, x), each entry 1 or 3 and at least
+    one 3: (3,3,3) is the 27-sample filter, (1,3,3) the in-plane one for thick slices; out: an int16 contiguous tensor
+    of the image's shape that shares no storage with it (default: a new one).  -> out.  Fewer than 2^31 voxels.  A
+    min / max selection network on integers: bit-identical from call to call; never synchronises; every check runs
+    before any launch."""
+    rz, ry, rx = (v // 2 for v in median_size("median_filter3d", size))
+    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
+        raise ValueError("median_filter3d: image must be a non-empty [D,H,W] tensor")
+    if image.dtype != torch.int16:
+        raise TypeError(f"median_filter3d: expected an int16 image, got {image.dtype}")
+    if image.numel() >= 2 ** 31:
+        raise ValueError("median_filter3d: volumes of 2^31 voxels or more are not supported")
+    if out is not None:
+        if not isinstance(out, Tensor) or out.dtype != torch.int16:
+            raise TypeError("median_filter3d: out must be an int16 tensor")
+        if tuple(out.shape) != tuple(image.shape) or not out.is_contiguous():
+            raise ValueError(f"median_filter3d: out must be contiguous and of the image's shape {tuple(image.shape)}")
+        if out.device != image.device:
+            raise ValueError("median_filter3d: out must live on the image's device")
+        if out.untyped_storage().data_ptr() == image.untyped_storage().data_ptr():
+            raise ValueError("median_filter3d: out must not share storage with image")
+    image = image.contiguous()
+    D, H, W = (int(v) for v in image.shape)
+    with launch_scope(image.device):
+        _req(image, "median_filter3d: image", torch.int16)
+        if out is None:
+            out = torch.empty_like(image)
+        _chk(_L().dram_median3d(_p(image), _p(out), D, H, W, rz, ry, rx, _stream()), "dram_median3d")
+    return out
+
+
 # --------------------------------------------------------------------------- heads / losses
 def head_fwd(x: Tensor, w: Tensor, bias: Tensor, lungs: Optional[Tensor], sigmoid: bool):
     """x [B,D,H,W,32] (float32 or bfloat16); w [NO,32]; lungs None or [B,Dl,Hl,Wl] full-res mask.  The dense maps

@@ -357,6 +357,20 @@ def laa_cluster_metrics(result: dict, names=None) -> dict:
     return out
 
 
+# --------------------------------------------------------------------------- the noise filter in front of the scan side
+def filtered_image(case_image: torch.Tensor, size=(3, 3, 3)) -> torch.Tensor:
+    """The scan-side input of ``densitometry`` / ``core_peel`` / ``laa_clusters`` with the noise filter in front:
+    ``ops.median_filter3d`` of ``prepare_case``'s 'image' (int16 [D,H,W]; ``size``: (3, 3, 3), (1, 3, 3), ...), a new
+    tensor.  At lung voxels it equals the crop of the filtered whole scan when the case was prepared with
+    ``dilate_iterations`` >= 1 and ``crop_border`` > 0.  Device work only."""
+    return ops.median_filter3d(case_image, size)
+
+
+def filter_name(size) -> str:
+    """'median{z}x{y}x{x}' of a window size: the value of the report's 'scan_filter' key."""
+    return "median{}x{}x{}".format(*ops.median_size("filter_name", size))
+
+
 # --------------------------------------------------------------------------- the sections of the report
 class _Section(NamedTuple):
     """One optional section of the predict report; ``_SECTIONS`` maps ``predict_case``'s switch to it.  Adding an analysis
@@ -432,7 +446,8 @@ def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=No
 def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[float], target_size: Sequence[int],
                  uid=None, want_u8: bool = True, regions: bool = False, region_names=None, densitometry: bool = False,
                  densitometry_kw: Optional[dict] = None, core_peel: bool = False, peel_mm: float = 10.0,
-                 clusters: bool = False, cluster_kw: Optional[dict] = None, **prepare_kw) -> dict:
+                 clusters: bool = False, cluster_kw: Optional[dict] = None, scan_filter=None,
+                 scan_filter_sections: Sequence[str] = ("densitometry", "core_peel", "clusters"), **prepare_kw) -> dict:
     """One scan + its lobe segmentation -> its entry of ``build_outputs``: ``transforms.prepare_case`` (dataset.py:57-92)
     -> ``transforms.prepare_sample(target_size)`` -> a batch of one -> ``module.predict_step`` -> ``build_outputs``.
     The composition only; `prepare_kw` goes to ``prepare_case`` (crop_border, dilate_iterations, ...).  ``regions``:
@@ -454,7 +469,28 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     ``clusters`` (independent of the three): the entry also carries ``laa_cluster_metrics`` of ``laa_clusters`` on the
     case's 'image' and 'lobe_labels' before the resize (``cluster_kw``: n_regions, threshold, connectivity), keyed
     through ``region_names``, and a line in error_messages when LAA voxels carry a label above n_regions.
-    'full_cle' / 'full_pse' are the same bit for bit under every combination."""
+    'full_cle' / 'full_pse' are the same bit for bit under every combination.
+
+    ``scan_filter`` (None, or a window size of ``ops.median_filter3d``: (3, 3, 3) or (1, 3, 3), ...):
+    the sections named in ``scan_filter_sections`` that are switched on read ``filtered_image`` of the case's 'image',
+    filtered once, instead of the image itself; a section that is not named reads the raw one.  Only the scan side
+    changes: the network's input, the masks, ``regions`` and the network side of ``core_peel`` (the zones depend on the
+    labels alone) are those of the raw scan, bit for bit.  The metrics then end with 'scan_filter': 'median3x3x3' /
+    'median1x3x3' (``filter_name``); with the filter off the key is absent and the entry is what it is without the
+    argument.  It is an option for noisy scans, and no value of it is recommended.  ValueError, before any device work,
+    for a bad size, a name in ``scan_filter_sections`` that is no scan-side section, and ``scan_filter`` together with
+    ``dilate_iterations`` < 1 or ``crop_border`` <= 0: only with a dilation and a padded crop does every window centred
+    on a lung voxel hold the scan's own values, so that the filtered crop equals the crop of the filtered scan there."""
+    named = tuple(scan_filter_sections)
+    for name in named:
+        if name not in _SECTIONS or _SECTIONS[name].run is None:
+            raise ValueError(f"predict_case: scan_filter_sections: {name!r} is not a scan-side section "
+                             f"{tuple(k for k, v in _SECTIONS.items() if v.run is not None)}")
+    if scan_filter is not None:
+        scan_filter = ops.median_size("predict_case: scan_filter", scan_filter)
+        if int(prepare_kw.get("dilate_iterations", 2)) < 1 or not prepare_kw.get("crop_border", 5) > 0:
+            raise ValueError("predict_case: scan_filter needs dilate_iterations >= 1 and crop_border > 0: without them a "
+                             "window centred on a lung voxel reaches the fill value or the crop's edge")
     on = {"regions": bool(regions), "densitometry": bool(densitometry), "core_peel": bool(core_peel),
           "clusters": bool(clusters)}
     kw = {"densitometry": dict(densitometry_kw or {}), "clusters": dict(cluster_kw or {})}
@@ -465,7 +501,10 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
             raise ValueError(f"predict_case: core_peel splits the module's n_regions = {n} lobes; densitometry_kw asks "
                              "for another count")
     case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=any(on.values()), **prepare_kw)
-    results = {name: _SECTIONS[name].run(case["image"], case["lobe_labels"], spacing, **kw[name])
+    filtered = scan_filter is not None and any(on[name] for name in named)
+    smooth = filtered_image(case["image"], scan_filter) if filtered else None
+    results = {name: _SECTIONS[name].run(smooth if filtered and name in named else case["image"], case["lobe_labels"],
+                                         spacing, **kw[name])
                for name in _LAUNCH_ORDER if on[name]}
     cp = results.get("core_peel")
     # core / peel rides the network side on the regions' tail: its zone labels are the batch's labels, with 2n regions
@@ -494,6 +533,8 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
             outside, n = section.outside(results[name])
             if outside > 0:
                 entry["error_messages"].append(section.error.format(outside, n))
+    if filtered:
+        entry["metrics"]["scan_filter"] = filter_name(scan_filter)
     return entry
 
 

@@ -743,6 +743,16 @@ int dram_label_components(const void* key_or_labels, int lab_elem, long long str
                           int32_t* components, int32_t* cluster_voxels, int64_t* table, void* work, int D, int H, int W,
                           dram_stream_t stream);
 
+/* 3-D median filter of an int16 volume (csrc/median.hip; definitions: INTEGRATION.md B9): out[z,y,x] = the median of
+ * the (2rz+1)(2ry+1)(2rx+1) values of `in` in the window centred on the voxel, each radius 0 or 1 (3, 9 or 27 samples;
+ * (1,1,1) is the 3x3x3 filter, (0,1,1) the in-plane 3x3 one), indices clamped to the volume (edges replicated:
+ * scipy.ndimage.median_filter(mode='nearest')).  in, out [D,H,W] contiguous, out != in; `in` is only read.
+ * One launch, every output element written; a min / max selection network on integers: exact, no atomics, no
+ * workspace, never synchronises, capturable; bit-identical from call to call.
+ * Null pointer, a size < 1, a radius other than 0 / 1, all three radii 0, out == in: DRAM_ERR_BAD_ARG.
+ * D*H*W >= 2^31: DRAM_ERR_UNSUPPORTED. */
+int dram_median3d(const int16_t* in, int16_t* out, int D, int H, int W, int rz, int ry, int rx, dram_stream_t stream);
+
 /* Train-time augmentations (models.py:66-74) with GIVEN parameters, fused into one gather pass:
  * GaussianAddictive (intensity_transforms.py:145-177; noise [D,H,W] supplied by the caller, minmax[2] = volume
  * {min, max} on the device, e.g. folded from dram_minmax partials [nblk][2]), BoxMaskOut (:180-237), Flip
