@@ -256,7 +256,9 @@ __global__ __launch_bounds__(256, 2) void stem_bf16_wgrad_kernel(const float* __
         if (i >= 1) row[12 + i - 1] = v;                                   // the image shifted by one
       }
     }
-    // dy tile by LDS-DMA: granule p -> (cb, voxel, slot); out-of-range voxels read zeros (empty offset)
+    // dy tile by LDS-DMA: granule p -> (cb, voxel, slot); out-of-range voxels read zeros (empty offset).  The
+    // resource's 32-bit byte offset (and its clamped size) covers a dy below 4 GiB = 2^31 bf16 elements only; the
+    // networks' largest stem output has 2^29, and dram_stem_fwd_bf16 refuses 2^31 or more.
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<char*>(reinterpret_cast<const char*>(dy)), 0, (int)(dybytes > 0xffffffffL ? 0xffffffffL : dybytes), BUF_FLAGS);
 #pragma unroll
@@ -337,8 +339,11 @@ __global__ __launch_bounds__(256) void stem_bf16_wgrad_reduce_kernel(const float
 }
 
 inline int wgrad_blocks(int total) { return total < 512 ? total : 512; }
+inline int fwd_blocks(int ntile) { return ntile < 512 ? ntile : 512; }
 
 }  // namespace
+
+extern "C" int dram_stem_fwd_blocks(int ntile) { return fwd_blocks(ntile); }
 
 // bf16-MFMA forms of dram_stem_fwd_bf16 / dram_stem_bwd_weight_bf16 (stem.hip keeps the fp32-MFMA forms with a bf16
 // store / load; DRAM_STEM_BF16=0 selects those: A/B, tests)
@@ -356,7 +361,7 @@ extern "C" int dram_stem_fwd_bf16mm(const float* x, const float* w, void* y, flo
   const double vo = (double)B * g.Do * g.Ho * g.Wo;
   DramProf prof(DRAM_FAM_STEM, 2, 2.0 * (double)g.ntile * 256.0 * 64.0 * 448.0,
                 4.0 * ((double)B * D * H * W + 64.0 * 343.0) + 2.0 * vo * 64.0, (hipStream_t)stream, 2.0 * vo * 64.0 * 343.0);
-  hipLaunchKernelGGL(stem_bf16_fwd_kernel, dim3(g.ntile < 512 ? g.ntile : 512), dim3(256), 0, (hipStream_t)stream, x, w,
+  hipLaunchKernelGGL(stem_bf16_fwd_kernel, dim3(fwd_blocks(g.ntile)), dim3(256), 0, (hipStream_t)stream, x, w,
                      (bf16_t*)y, stats_partial, g);
   DRAM_LAUNCH_CHECK();
   return DRAM_OK;

@@ -834,6 +834,9 @@ int dram_stem_fwd_bf16mm(const float* x, const float* w, void* y, float* stats_p
                          dram_stream_t stream);
 int dram_stem_bwd_weight_bf16mm(const float* x, const void* dy, float* dw, int B, int D, int H, int W, void* workspace,
                                 size_t workspace_bytes, dram_stream_t stream);
+/* workgroups dram_stem_fwd_bf16mm launches for ntile = dram_stem_num_tiles(...) tiles (persistent: each walks
+ * ceil(ntile / blocks) tiles at most) */
+int dram_stem_fwd_blocks(int ntile);
 int dram_bn_apply_bf16(const void* y, const float* scale, const float* shift, const void* residual, int Dr, int Hr,
                        int Wr, int Cr, int rs, void* z, int B, int D, int H, int W, int C, int relu,
                        dram_stream_t stream);

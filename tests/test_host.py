@@ -33,6 +33,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     bad = _lib.DramConvDesc(2, 16, 32, 32, 64, 15, 32, 32, 128, 3, 1, 4, 4)
     assert lib.dram_conv_num_mtiles(ctypes.byref(bad)) == -1            # inconsistent output dims rejected
     assert lib.dram_stem_num_tiles(2, 64, 128, 128) == 2 * 16 * 16 * 16
+    assert [lib.dram_stem_fwd_blocks(n) for n in (1, 24, 8192)] == [1, 24, lib.dram_stem_fwd_blocks(1 << 30)]   # persistent
     assert ctypes.sizeof(_lib.DramTensorRef) == 40 and ctypes.sizeof(_lib.DramChunkRef) == 16
 
 
