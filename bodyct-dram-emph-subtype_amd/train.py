@@ -11,8 +11,13 @@ train.py:70,100-104).  Checkpoints are Lightning-1.9-shaped dicts (``state_dict`
 ``epoch``, ``global_step``) so they interoperate with the reference's loaders
 (test.py:66-72, processor.py:85-87).
 
-The reference's DataModule (SimpleITK / COPDGene cache) is out of scope; ``--synthetic``
-(default) feeds batches with the reference's batch contract (models.py:541-548).
+Data: ``--synthetic 1`` (the default) feeds random batches with the reference's batch contract
+(models.py:541-548).  ``--synthetic 0`` trains from the reference's archive (``--data_path``: a folder of
+``<SeriesInstanceUID>.pth`` cases beside ``merged.csv``; ``--train_csv`` / ``--valid_csv`` / ``--test_csv``), as the
+reference's DataModule does (models.py:99-157): train draws class-balanced through ``SubtypingStratifiedSampler`` with
+``--num_samples`` draws per class and epoch, the per-class loss weights start from that sampler's, validation reads
+``--valid_csv`` every epoch and the final test ``--test_csv`` (``--valid_csv`` when that is empty); ``dataset.ArchiveLoader``
+prepares every sample on the device.  The reference's SimpleITK reading (predict side) is ``predict_case``'s business.
 """
 from __future__ import annotations
 
@@ -69,7 +74,54 @@ def build_parser() -> ArgumentParser:
     # activation-map sheets of the first N validation / test batches (the reference's _draw_predictions, which
     # hard-codes N = 50), written on rank 0 under <model_path>/debug_input_data/<epoch>/<stage>/
     p.add_argument("--draw_predictions", default=0, type=int)
+    p.add_argument("--prefetch", default=2, type=int, help="--synthetic 0: cases the reader thread loads ahead")
     return p
+
+
+def check_archive_args(args) -> None:
+    """``--synthetic 0`` needs the archive and the training split; said before anything else is set up."""
+    if args.synthetic:
+        return
+    missing = [f"--{k}" for k in ("data_path", "train_csv") if not getattr(args, k)]
+    if missing:
+        raise SystemExit(f"--synthetic 0 trains from a scan archive and requires {' and '.join(missing)} "
+                         "(--data_path: the folder with merged.csv and the <SeriesInstanceUID>.pth cases)")
+    if not os.path.isdir(args.data_path):
+        raise SystemExit(f"--data_path {args.data_path!r} is not a folder")
+    if args.prefetch < 1:
+        raise SystemExit("--prefetch must be >= 1")
+
+
+def build_archive_data(args, module, rank, world, device, augment=None):
+    """The three loaders of ``--synthetic 0`` (train, validation, test), models.py:99-157; sets the module's per-class
+    loss weights to the train sampler's (models.py:249-252, :556-561), where the epoch-end rescale takes them from."""
+    from .data_sampler import SubtypingStratifiedSampler
+    from .dataset import ArchiveLoader, COPDGeneSubtyping
+
+    def split(csv_file):
+        uids = COPDGeneSubtyping.get_series_uids(csv_file)
+        if not uids:
+            raise SystemExit(f"{csv_file!r} names no SeriesInstanceUID (missing file, or no such column)")
+        return COPDGeneSubtyping(args.data_path, uids)
+
+    def sequential(ds):
+        return ArchiveLoader(ds, args.batch_size, args.target_size, device, shuffle=False, drop_last=False, rank=rank,
+                             world=world, seed=args.seed, prefetch=args.prefetch)
+
+    train_set = split(args.train_csv)
+    sampler = SubtypingStratifiedSampler(train_set, args.num_samples, seed=args.seed)
+    module.cle_class_weights = torch.tensor(sampler.cle_class_weights, dtype=torch.float32)
+    module.pse_class_weights = torch.tensor(sampler.pse_class_weights, dtype=torch.float32)
+    data = ArchiveLoader(train_set, args.batch_size, args.target_size, device, sampler=sampler, shuffle=True,
+                         drop_last=True, rank=rank, world=world, seed=args.seed, prefetch=args.prefetch, augment=augment)
+    if len(data) < 1:
+        raise SystemExit(f"--num_samples {args.num_samples} x {len(sampler.cle_label_groups)} classes gives no full "
+                         f"batch of {args.batch_size} on {world} rank(s)")
+    if not args.valid_csv:
+        logging.warning("--valid_csv is empty: validating on the cases of --train_csv")
+    val_set = split(args.valid_csv) if args.valid_csv else train_set
+    test_set = split(args.test_csv) if args.test_csv else val_set
+    return data, sequential(val_set), sequential(test_set)
 
 
 class SyntheticSubtypeData:
@@ -145,6 +197,7 @@ def restore(module, optimizer, scheduler, path, reload_only_weights: bool):
 
 def run_training_job(argv=None):
     args = build_parser().parse_args(argv)
+    check_archive_args(args)
     args.exp_name = f"subtyping_{args.model_arch}"
     exp_path = Path(args.model_path) / args.exp_name
     ckp_path = exp_path / "checkpoints"
@@ -180,10 +233,16 @@ def run_training_job(argv=None):
     if world > 1:
         from . import distributed as ddist
         ddist.attach(module.model)                 # DDP + SyncBatchNorm semantics (train.py:100-104)
-    data = SyntheticSubtypeData(args.num_samples, args.batch_size, args.target_size, rank, world, device, args.seed)
-    val_data = SyntheticSubtypeData(max(args.batch_size * world, args.num_samples // 4), args.batch_size, args.target_size,
-                                    rank, world, device, args.seed + 7)
     augment = TrainAugment() if getattr(args, "augment", 0) else None        # models.py:66-74 (train mode only)
+    if args.synthetic:
+        data = SyntheticSubtypeData(args.num_samples, args.batch_size, args.target_size, rank, world, device, args.seed)
+        val_data = SyntheticSubtypeData(max(args.batch_size * world, args.num_samples // 4), args.batch_size,
+                                        args.target_size, rank, world, device, args.seed + 7)
+        test_data, test_epoch = val_data, 10_000
+    else:
+        # the loader augments each sample as it prepares it: nothing is left for augment_batch
+        data, val_data, test_data = build_archive_data(args, module, rank, world, device, augment)
+        augment, test_epoch = None, 0
     global_step = 0                                # optimizer steps, as Lightning counts them
     accumulate = args.accumulate_grad_batches
     best = (float("inf"), None)
@@ -243,7 +302,7 @@ def run_training_job(argv=None):
         from . import ops
         ops.weights_changed()
         module.eval()
-        test_outputs = [module.test_step(b, i) for i, b in enumerate(val_data.epoch(10_000))]
+        test_outputs = [module.test_step(b, i) for i, b in enumerate(test_data.epoch(test_epoch))]
         te = module.test_epoch_end(test_outputs)
         if rank == 0:
             logging.info(f"test (best = {best_path}): acc cle/pse {float(te['acc_cle']):.3f}/{float(te['acc_pse']):.3f}")

@@ -102,6 +102,143 @@ def prepare_sample(sample: Dict[str, torch.Tensor], target_size: Sequence[int]) 
     return out
 
 
+# --------------------------------------------------------------------------- archive case -> training sample
+_SAMPLE_KEYS = ("image", "lung_mask", "em_mask")
+_MAX_SPAN = 4095                   # sum c^2 over < 2^31 voxels stays inside int64 (dram_sample_stats_i16)
+
+
+def _int_span(fn: str, from_span) -> Tuple[int, int]:
+    """``from_span`` as the integer pair the int16 kernels take; ValueError for anything they cannot represent."""
+    lo, hi = float(from_span[0]), float(from_span[1])
+    if not (lo.is_integer() and hi.is_integer()):
+        raise ValueError(f"{fn}: from_span {tuple(from_span)} is not integral, which the int16 path needs: pass the "
+                         "image as float (image.float()) to window it with this span")
+    if not (lo < hi and hi - lo <= _MAX_SPAN and -65536 <= lo and hi <= 65536):
+        raise ValueError(f"{fn}: from_span {tuple(from_span)} must satisfy lo < hi, hi - lo <= {_MAX_SPAN} and lie in "
+                         "-65536..65536 on the int16 path: pass the image as float for any other span")
+    return int(lo), int(hi)
+
+
+def sample_window_sums(scan: torch.Tensor, from_span=FROM_SPAN) -> torch.Tensor:
+    """scan: int16 device tensor of n >= 2 elements (contiguous; the base may be 2-byte aligned only) -> int64
+    [nblk, 2]: per-block ``{sum c, sum c^2}``, c = clamp(x, lo, hi) - lo.  Exact; the column sums do not depend on
+    how the blocks are cut.  One launch, nothing read back."""
+    fn = "sample_window_sums"
+    if not isinstance(scan, torch.Tensor) or scan.dtype != torch.int16:
+        raise TypeError(f"{fn}: expected an int16 tensor, got {getattr(scan, 'dtype', type(scan))}")
+    lo, hi = _int_span(fn, from_span)
+    n = scan.numel()
+    if not 2 <= n < 2 ** 31:
+        raise ValueError(f"{fn}: needs 2 <= n < 2^31 elements, got {n}")
+    if not scan.is_cuda:
+        raise TypeError(f"{fn}: expected a device tensor (libdram_hip has no CPU path)")
+    with ops.launch_scope(scan.device):
+        _req(scan, "scan", torch.int16)
+        partial = torch.empty((_L().dram_sample_stats_nblk(n), 2), device=scan.device, dtype=torch.int64)
+        _chk(_L().dram_sample_stats_i16(_p(scan), _p(partial), n, lo, hi, _stream()), "dram_sample_stats_i16")
+    return partial
+
+
+def _below(image: torch.Tensor, threshold) -> torch.Tensor:
+    """image < threshold; for an integer image without torch's wrap of a scalar its dtype cannot hold"""
+    if image.is_floating_point():
+        return image < threshold
+    info, t = torch.iinfo(image.dtype), int(math.ceil(threshold))         # x < t  <=>  x < ceil(t) for an integer x
+    if t > info.max:
+        return torch.ones_like(image, dtype=torch.bool)
+    return image < max(t, info.min)
+
+
+def _sample_out(fn: str, out, shape, device):
+    """The three destinations of ``prepare_archive_sample`` as (image f32, lung uint8, em uint8, returned dict)."""
+    if out is None:
+        img = torch.empty(shape, device=device, dtype=torch.float32)
+        lung = torch.empty(shape, device=device, dtype=torch.uint8)
+        em = torch.empty(shape, device=device, dtype=torch.uint8)
+        return img, lung, em, {"image": img, "lung_mask": lung.view(torch.bool), "em_mask": em.view(torch.bool)}
+    if not isinstance(out, dict) or any(k not in out for k in _SAMPLE_KEYS):
+        raise ValueError(f"{fn}: out must be a dict with the keys {_SAMPLE_KEYS}")
+    views = []
+    for k in _SAMPLE_KEYS:
+        t = out[k]
+        want = (torch.float32,) if k == "image" else (torch.bool, torch.uint8)
+        if not isinstance(t, torch.Tensor) or t.dtype not in want:
+            raise TypeError(f"{fn}: out[{k!r}] must be a {' / '.join(str(w) for w in want)} tensor")
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError(f"{fn}: out[{k!r}] must be a dense {tuple(shape)} block, got shape {tuple(t.shape)} "
+                             f"strides {t.stride()}")
+        if t.device != device:
+            raise ValueError(f"{fn}: out[{k!r}] lives on {t.device}, the case on {device}")
+        views.append(t.view(torch.uint8) if t.dtype == torch.bool else t)
+    return views[0], views[1], views[2], {k: out[k] for k in _SAMPLE_KEYS}
+
+
+def prepare_archive_sample(image: torch.Tensor, lung_mask: torch.Tensor, target_size: Sequence[int], out=None,
+                           from_span=FROM_SPAN, em_threshold=-950) -> Dict[str, torch.Tensor]:
+    """One case of the training archive (dataset.py:147-155: 'image' [D,H,W] raw HU, 'lung_mask') -> the sample the
+    step trains on: {'image': float32 [Do,Ho,Wo] windowed, z-scored and resized, 'lung_mask': bool, 'em_mask': bool},
+    em_mask = (image < em_threshold) & (lung_mask > 0) taken at full size (dataset.py:149), both masks resized nearest.
+
+    ``out``: optional dict of the three destinations, dense [Do,Ho,Wo] views such as ``batch[k][b]`` (masks bool or
+    uint8); they are written in place and returned.
+
+    An int16 image with a uint8 / bool / int16 mask and an integral ``from_span`` takes the fused path of
+    csrc/sample_prep.hip: one exact integer statistics pass and one output pass over the int16 data, two launches plus
+    O(nblk) glue, nothing read back, no full-size temporary.  Any other dtype takes the composition ``prepare_image`` +
+    ``prepare_mask`` (float32 copies of the full-size volumes).  Shapes, ``target_size``, host tensors and a span the
+    int16 path cannot take are refused (ValueError / TypeError) before the device is touched."""
+    fn = "prepare_archive_sample"
+    for t, name in ((image, "image"), (lung_mask, "lung_mask")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{fn}: {name} must be a tensor, got {type(t)}")
+    if image.dim() != 3 or min(image.shape) < 1 or tuple(image.shape) != tuple(lung_mask.shape):
+        raise ValueError(f"{fn}: image {tuple(image.shape)} and lung_mask {tuple(lung_mask.shape)} must be one "
+                         "non-empty [D,H,W] shape")
+    try:
+        target = tuple(int(v) for v in target_size)
+        if any(t != v for t, v in zip(target, target_size)):
+            target = ()
+    except (TypeError, ValueError):
+        target = ()
+    if len(target) != 3 or min(target) < 1:
+        raise ValueError(f"{fn}: target_size must be three positive integers, got {target_size!r}")
+    if image.numel() >= 2 ** 31 or target[0] * target[1] * target[2] >= 2 ** 31:
+        raise ValueError(f"{fn}: volumes of 2^31 voxels or more are not supported")
+    if image.numel() < 2:
+        raise ValueError(f"{fn}: the statistics need at least two voxels")
+    fused = image.dtype == torch.int16 and lung_mask.dtype in (torch.uint8, torch.bool, torch.int16)
+    if image.dtype == torch.int16:
+        lo, hi = _int_span(fn, from_span)
+    if not (image.is_cuda and lung_mask.is_cuda) or image.device != lung_mask.device:
+        raise TypeError(f"{fn}: image and lung_mask must be tensors on one device (libdram_hip has no CPU path)")
+    o_img, o_lung, o_em, ret = _sample_out(fn, out, target, image.device)
+    if not fused:
+        o_img.copy_(prepare_image(image, target, from_span))
+        lung = lung_mask > 0
+        o_lung.copy_(prepare_mask(lung, target))
+        o_em.copy_(prepare_mask(_below(image, em_threshold) & lung, target))
+        return ret
+    D, H, W = (int(v) for v in image.shape)
+    n = image.numel()
+    thr = max(-32768, min(32768, int(math.ceil(em_threshold))))       # x < t  <=>  x < ceil(t) for an integer x
+    with ops.launch_scope(image.device):
+        scan = _req(image.contiguous(), "image", torch.int16)
+        lung = lung_mask.contiguous()
+        if lung.dtype == torch.bool:
+            lung = lung.view(torch.uint8)
+        _req(lung, "lung_mask", lung.dtype)
+        s = sample_window_sums(scan, (lo, hi)).sum(0).double()        # exact int64 column sums -> float64 glue
+        span = float(hi - lo)
+        mean = s[0] / n / span
+        var = (s[1] - s[0] * s[0] / n) / (n - 1) / (span * span)       # torch.std(): unbiased
+        mean_inv = torch.stack([mean, var.clamp_min(0).rsqrt()]).float().contiguous()
+        zidx = depth_indices(D, target[0], image.device)
+        _chk(_L().dram_prep_sample_i16(_p(scan), _p(lung), 2 if lung.dtype == torch.int16 else 1, _p(zidx), _p(mean_inv),
+                                       _p(o_img), _p(o_lung), _p(o_em), D, H, W, *target, lo, hi, thr, _stream()),
+             "dram_prep_sample_i16")
+    return ret
+
+
 # --------------------------------------------------------------------------- scan + lobes -> prepared predict case
 def _lobes_operand(lobes: torch.Tensor):
     """(tensor the kernels read, its lobe_dtype code): uint8 / bool and int16 volumes are read as they are, anything

@@ -6,7 +6,8 @@ requiring hydra/omegaconf (absent from this image): the yaml is read with PyYAML
 ``med3d.*`` target is bound to THIS package's drop-in ``med3d`` module.  If hydra is
 installed and this directory is on ``sys.path`` (so that ``import med3d`` finds the
 drop-in), the reference's own ``get_model_by_name`` works unchanged.
-``load_state_dict_greedy`` keeps the semantics of reference utils.py:226-249 (own implementation).
+``load_state_dict_greedy`` keeps the semantics of reference utils.py:226-249 (own implementation),
+``read_csv_in_dict`` those of utils.py:200-210 (the csv reader of the training archive, dataset.py).
 """
 from __future__ import annotations
 
@@ -14,6 +15,7 @@ if not __package__:          # imported top-level (this directory on sys.path): 
     import _dropin
     __package__ = _dropin.adopt(__name__)
 
+import csv
 import importlib
 import logging
 import os
@@ -62,6 +64,20 @@ def load_state_dict_greedy(model: torch.nn.Module, state_dict_to_load: Dict):
     report("[load_state_dict_greedy] loaded %d/%d tensors; shape mismatch: %s; unexpected: %s; missing: %s",
            len(usable), len(have), mismatched or "-", unexpected or "-", missing or "-")
     return dict(mismatched=mismatched, unexpected=unexpected, missing=missing)
+
+
+def read_csv_in_dict(csv_file_path: str, column_key: str, fieldnames=None):
+    """utils.py:200-210: ({row[column_key]: row}, field names) of a comma-separated file with a header line (or the
+    given ``fieldnames``); a later row with the same key replaces an earlier one.  A missing file gives ({}, None)."""
+    rows: Dict[str, dict] = {}
+    if not os.path.exists(csv_file_path):
+        return rows, None
+    with open(csv_file_path, "rt", newline="") as fp:
+        reader = csv.DictReader(fp, delimiter=",", fieldnames=fieldnames)
+        for row in reader:
+            rows[row[column_key]] = row
+        names = reader.fieldnames
+    return rows, names
 
 
 def cat_all_gather(t: torch.Tensor) -> torch.Tensor:

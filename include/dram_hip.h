@@ -641,6 +641,30 @@ int dram_prep_image(const float* scan, const int* zidx, const float* mean_invstd
 int dram_prep_mask(const float* mask, const int* zidx, float* out, int D, int H, int W, int Do, int Ho, int Wo,
                    dram_stream_t stream);
 
+/* One archive case -> one training sample straight from the int16 data (csrc/sample_prep.hip; dataset.py:147-155 with
+ * the transforms above): two launches, no float32 copy of a full-size volume.
+ *   dram_sample_stats_i16: scan [n] int16 (any 2-byte-aligned base, any n >= 2); c = clamp(x, lo, hi) - lo per voxel;
+ *     partial [dram_sample_stats_nblk(n)][2] int64, row b = {sum c, sum c^2} over block b's share (every row is written:
+ *     no memset).  Integer sums, no atomics: exact, bit-identical from call to call.  The windowed value of the reference
+ *     is c / (hi - lo), so with S1, S2 the column sums: mean = S1 / n / (hi - lo),
+ *     var (unbiased) = (S2 - S1^2 / n) / (n - 1) / (hi - lo)^2 -- the caller's float64 glue on [nblk][2].
+ *   dram_prep_sample_i16: one pass over the output grid.  scan [D,H,W] int16; lung [D,H,W] of lung_dtype 1 (uint8 / bool)
+ *     or 2 (int16); zidx [Do] and mean_invstd [2] as for dram_prep_image.  Per output voxel:
+ *       out_image = (bilinear(window(scan[zidx[z]]))(y, x) - mean) * invstd, dram_prep_image's arithmetic on the (exactly)
+ *         converted taps;
+ *       out_lung  = lung[nn] > 0 (signed for int16), nn the nearest source voxel of dram_prep_mask;
+ *       out_em    = scan[nn] < em_threshold && lung[nn] > 0
+ *     -- the masks equal thresholding at full size and resizing afterwards (dataset.py:149, spatial_transforms.py:77-97).
+ *     out_image (float), out_lung, out_em (bytes 0 / 1): dense [Do,Ho,Wo] blocks at any base, e.g. one slot of a batch.
+ * Neither call synchronises; both can be captured.
+ * A null pointer, a size < 1, n < 2, hi <= lo, hi - lo > 4095, lo or hi outside -65536..65536, lung_dtype not 1 / 2:
+ * DRAM_ERR_BAD_ARG.  n, D*H*W or Do*Ho*Wo >= 2^31: DRAM_ERR_UNSUPPORTED. */
+int dram_sample_stats_nblk(long long n);
+int dram_sample_stats_i16(const int16_t* scan, long long* partial, long long n, int lo, int hi, dram_stream_t stream);
+int dram_prep_sample_i16(const int16_t* scan, const void* lung, int lung_dtype, const int* zidx, const float* mean_invstd,
+                         float* out_image, uint8_t* out_lung, uint8_t* out_em, int D, int H, int W, int Do, int Ho, int Wo,
+                         int lo, int hi, int em_threshold, dram_stream_t stream);
+
 /* Predict post-processing (processor.py:111-129, :143): src [D,H,W] resized (trilinear, align_corners=True) to
  * the lung-crop size (rd,rh,rw) and pasted at offset (oz,oy,ox) into a zero volume of the original grid
  * [Do,Ho,Wo]; out_f32 and/or out_u8 (= utils.windowing(., (0,1) -> (0,255)) truncated to uint8). */
