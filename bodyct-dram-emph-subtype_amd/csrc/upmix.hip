@@ -18,10 +18,12 @@
 //   pass X: outer = (B, nz, ny), m = (kz, ky);   pass Y: outer = (B, nz), m = (vx, kz);   pass Z: outer = B, m = (vy, vx)
 // (the tap index of b is t = (kz * 3 + ky) * 3 + kx: each pass contracts the innermost remaining tap).  The last pass
 // adds the skip convolution's result (bias included), stores in the storage type and takes the BatchNorm partial sums
-// of the stored values, like a convolution epilogue.  Backward = the exact transposes in reverse order (a gather per
+// of the stored values, like a convolution epilogue.  Backward = the transposes in reverse order (a gather per
 // low-resolution element: no atomics), followed by the 1x1x1 data / weight gradient GEMMs at the low resolution.
-// Intermediates between the passes are fp32 whatever the storage type.  Same interpolation arithmetic as
-// upcat_fwd_kernel (lin_src: PyTorch's align_corners source index).
+// Intermediates between the passes are fp32 whatever the storage type.  Indices as in upcat_fwd_kernel (lin_src:
+// PyTorch's align_corners source index); the same indices forward and backward, so the two operators have the same
+// support, but NOT bit for bit the same weights: the forward passes take w1 = fma(scale, u, -i0) (lin_src_fused below),
+// the transposed pass lin_src's w1 = fl(scale * u) - i0 as compiled -- up to (Ni + 1) * 2^-24 apart.
 #include "common.h"
 
 namespace {
@@ -30,8 +32,24 @@ __device__ __forceinline__ float4 f4_fma(const float w, const float4 a, const fl
   return make_float4(fmaf(w, a.x, acc.x), fmaf(w, a.y, acc.y), fmaf(w, a.z, acc.z), fmaf(w, a.w, acc.w));
 }
 
+__device__ __forceinline__ float4 f4_sel(const bool keep, const float4 a) {
+  return make_float4(keep ? a.x : 0.f, keep ? a.y : 0.f, keep ? a.z : 0.f, keep ? a.w : 0.f);
+}
+
+// lin_src's indices with the weight as the forward passes have always been compiled: w1 is ONE fma, the product scale * dst
+// unrounded (lin_src leaves that fusion to the optimiser, which drops it as soon as a branch separates the product from
+// the subtraction).  Written out, so that the passes' bits do not depend on the code around them.
+__device__ __forceinline__ void lin_src_fused(int dst, float scale, int in, int& i0, int& i1, float& w0, float& w1) {
+  const float d = (float)dst;
+  i0 = (int)(scale * d);
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  w1 = fmaf(scale, d, -(float)i0);
+  w0 = 1.f - w1;
+}
+
 // one output element (4 channels) of the generic pass
-template <typename TIN>
+template <typename TIN, bool WAVE_SKIP>
 __device__ __forceinline__ float4 axis_gather(const TIN* __restrict__ in, const long o, const int v, const int mi,
                                               const int c4, const int Ni, const int m, const int C, const float scale) {
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -39,18 +57,28 @@ __device__ __forceinline__ float4 axis_gather(const TIN* __restrict__ in, const 
   // per-lane `continue` around each pair kept two loads in flight)
   float4 x0[3], x1[3];
   float w0[3], w1[3];
+  bool ok[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int u = v + k - 1;
-    const bool ok = u >= 0 && u < 2 * Ni;
+    ok[k] = u >= 0 && u < 2 * Ni;
     const int uc = u < 0 ? 0 : (u >= 2 * Ni ? 2 * Ni - 1 : u);
     int i0, i1;
-    lin_src(uc, scale, Ni, i0, i1, w0[k], w1[k]);
-    if (!ok) { w0[k] = 0.f; w1[k] = 0.f; }
+    lin_src_fused(uc, scale, Ni, i0, i1, w0[k], w1[k]);
+    if (!ok[k]) { w0[k] = 0.f; w1[k] = 0.f; }
     const long base = ((long)mi * 3 + k) * C + 4 * c4;
     const long row = (long)m * 3 * C;
     x0[k] = ld4<TIN>(in, (o * Ni + i0) * row + base);
     x1[k] = ld4<TIN>(in, (o * Ni + i1) * row + base);
+  }
+  // What an out-of-range tap loaded is replaced by zero, not only weighted by zero: 0 * Inf = NaN would otherwise reach
+  // a border output from an element the operator never reads.  Only the rows v = 0 (tap 0) and v = 2 Ni - 1 (tap 2)
+  // have such a tap.  WAVE_SKIP: a wave without one skips the 16 selects per lane (they cost the one-output-per-thread
+  // kernel 0.6 / 1.5 us of its 99 / 61 us passes; the last pass, which loops, nothing -- and there the branch costs
+  // registers: 54 -> 66, seven waves per SIMD instead of eight).
+  if (!WAVE_SKIP || __any(!(ok[0] && ok[2]))) {
+    x0[0] = f4_sel(ok[0], x0[0]); x1[0] = f4_sel(ok[0], x1[0]);
+    x0[2] = f4_sel(ok[2], x0[2]); x1[2] = f4_sel(ok[2], x1[2]);
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -72,7 +100,7 @@ __global__ __launch_bounds__(256) void upmix_axis_fwd_kernel(const TIN* __restri
   const int mi = (int)(r % m); r /= m;
   const int v = (int)(r % (2 * Ni));
   const long o = r / (2 * Ni);
-  st4<float>(out, 4 * i, axis_gather<TIN>(in, o, v, mi, c4, Ni, m, C, scale));
+  st4<float>(out, 4 * i, axis_gather<TIN, true>(in, o, v, mi, c4, Ni, m, C, scale));
 }
 
 // last pass: + base (the skip convolution's output, may alias out), stored as T, BatchNorm partial sums of the STORED
@@ -95,7 +123,7 @@ __global__ __launch_bounds__(256) void upmix_axis_fwd_final_kernel(const float* 
     const long r = vox / m;
     const int v = (int)(r % (2 * Ni));
     const long o = r / (2 * Ni);
-    float4 a = axis_gather<float>(in, o, v, mi, c4, Ni, m, C, scale);
+    float4 a = axis_gather<float, false>(in, o, v, mi, c4, Ni, m, C, scale);
     const long off = vox * C + 4 * c4;
     if (base) {
       const float4 bv = ld4<T>(base, off);
@@ -123,8 +151,8 @@ __global__ __launch_bounds__(256) void upmix_axis_fwd_final_kernel(const float* 
 
 // transposed pass:  H[o][n][m][k][c] = sum_u [i0(u) == n] w0(u) G[o][u - k + 1][m][c] + [i1(u) == n] w1(u) G[...]
 // over the u in [0, 2 Ni) with 0 <= u - k + 1 < 2 Ni.  Candidates: scale * u in (n - 1, n + 1); the window below is one
-// wider on both sides and every candidate is tested with the forward's own lin_src, so the two operators are exact
-// transposes whatever the rounding of scale * u.
+// wider on both sides and every candidate is tested with lin_src, whose indices are the forward's (lin_src_fused), so the
+// two operators have the same support whatever the rounding of scale * u; the weights are lin_src's own (header).
 template <typename TG, typename TH>
 __global__ __launch_bounds__(256) void upmix_axis_bwd_kernel(const TG* __restrict__ g, TH* __restrict__ h,
                                                              const long total, const int Ni, const int m, const int C,
