@@ -30,6 +30,21 @@
 // and writes the second, z reads the second: every element that is read was written by the launch before.  No
 // atomics, no ticket words, no waiting between workgroups, never synchronises; integer minima: bit-identical from call
 // to call.
+//
+// dram_lobe_zones adds the fissural rind: per lung voxel f2, the squared distance to the nearest SITE (a voxel whose
+// label is in 1..n) of another class than the voxel's own.  The answer depends on the voxel's class, so the separable
+// passes carry the two nearest sites of distinct classes per element, packed as two uint64 keys (d2 << 3) | class in
+// one 16-byte element:
+//   * For any query class q the minimum over the classes != q at one element is one of its two kept pairs (the first
+//     unless its class is q, then the second); the min-plus over a line is the minimum of those per-element answers plus
+//     their costs; so reducing the union of the candidates to its two smallest with distinct classes loses nothing.
+//     Exact, ties included: which of two tied classes is kept second changes no answer.
+//   * x reads the sites from the labels, y is the same windowed min-plus as above on pairs, both ending at
+//     (s k)^2 >= the larger kept distance; the cap argument carries over (a pair above max_um^2 is stored as +inf).
+//   * The last launch does the z pass of BOTH transforms: d2 through line_min on the pleural work volume, exactly as
+//     edt_z_kernel does (the x and y launches are edt_x_kernel / edt_y_kernel themselves, so zone 1 is dram_lung_zones'
+//     zone 1 by construction), and f2 for the voxel's own class only, skipped where no output needs it.
+// Five launches, two more work volumes of 16-byte pairs behind the pleural two; the same promises as above.
 #include "common.h"
 
 #include <cmath>
@@ -188,7 +203,222 @@ int check_sizes(int D, int H, int W, int sz_um, int sy_um, int sx_um) {
   return DRAM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ lobe to lobe
+// A kept pair: (squared distance << 3) | class, class 1..5; PAIR_INF (class bits 7) for "none".  Keys order by distance
+// first, so the smaller key is the nearer site; a tie between classes goes to the lower class, which no result sees.
+constexpr unsigned long long PAIR_INF = ~0ull;
+
+// Insert candidate c into the two smallest keys with distinct classes (k1 <= k2, class(k1) != class(k2) or k2 = inf).
+// Invariant: k1 is the minimum of everything inserted, k2 the minimum of everything whose class is not k1's.
+// Inserting PAIR_INF changes nothing.
+__device__ __forceinline__ void keep_two(unsigned long long& k1, unsigned long long& k2, unsigned long long c) {
+  if (((c ^ k1) & 7ull) == 0ull) {
+    k1 = min(k1, c);
+  } else if (c < k1) {
+    k2 = k1;                                                    // the old minimum: its class is not c's
+    k1 = c;
+  } else {
+    k2 = min(k2, c);
+  }
+}
+
+__device__ __forceinline__ void cap_two(unsigned long long& k1, unsigned long long& k2, unsigned long long cap2) {
+  if ((k1 >> 3) > cap2) k1 = PAIR_INF;                          // PAIR_INF >> 3 = 2^61 - 1 is above every cap
+  if ((k2 >> 3) > cap2) k2 = PAIR_INF;                          // k2 >= k1: a capped k1 takes k2 with it
+}
+
+// the squared distance of the first kept pair whose class is not cv (~0 for none)
+__device__ __forceinline__ unsigned long long foreign(const ulonglong2 p, unsigned cv) {
+  const unsigned long long k = ((unsigned)(p.x & 7ull) != cv) ? p.x : p.y;
+  return k == PAIR_INF ? ~0ull : k >> 3;
+}
+
+// x pass: sites are read from the labels themselves (a site is a label in 1..n); out[v] = the two nearest sites of
+// distinct classes within the row, within Kx voxels and the cap.
+template <typename LT>
+__global__ __launch_bounds__(TPB) void lobe_x_kernel(const LT* __restrict__ lab, long sz, long sy, int H, int W,
+                                                     unsigned total, unsigned long long s, int K, unsigned long long cap2,
+                                                     int n_regions, ulonglong2* __restrict__ out) {
+  const unsigned v = blockIdx.x * (unsigned)TPB + threadIdx.x;
+  if (v >= total) return;
+  const unsigned row = v / (unsigned)W;
+  const int x = (int)(v - row * (unsigned)W);
+  const LT* l = lab + (long)(row / (unsigned)H) * sz + (long)(row % (unsigned)H) * sy;
+  const int own = (int)l[x];
+  unsigned long long k1 = (own > 0 && own <= n_regions) ? (unsigned long long)own : PAIR_INF, k2 = PAIR_INF;
+  for (int k = 1; k <= K; ++k) {
+    const unsigned long long e = s * (unsigned long long)k, c = e * e;
+    if (c >= (k2 >> 3)) break;                                  // nothing further out can enter the two kept pairs
+    if (x - k >= 0) {
+      const int lb = (int)l[x - k];
+      if (lb > 0 && lb <= n_regions) keep_two(k1, k2, (c << 3) | (unsigned long long)lb);
+    }
+    if (x + k < W) {
+      const int lb = (int)l[x + k];
+      if (lb > 0 && lb <= n_regions) keep_two(k1, k2, (c << 3) | (unsigned long long)lb);
+    }
+  }
+  cap_two(k1, k2, cap2);
+  out[v] = make_ulonglong2(k1, k2);
+}
+
+// y pass: min-plus of the kept pairs along y, reduced to the two smallest with distinct classes again
+__global__ __launch_bounds__(TPB) void lobe_y_kernel(const ulonglong2* __restrict__ in, ulonglong2* __restrict__ out, int H,
+                                                     int W, unsigned total, unsigned long long s, int K,
+                                                     unsigned long long cap2) {
+  const unsigned v = blockIdx.x * (unsigned)TPB + threadIdx.x;
+  if (v >= total) return;
+  const int y = (int)(v / (unsigned)W % (unsigned)H);
+  const ulonglong2 f0 = in[v];
+  unsigned long long k1 = f0.x, k2 = f0.y;
+  for (int k = 1; k <= K; ++k) {
+    const unsigned long long e = s * (unsigned long long)k, c = e * e;
+    if (c >= (k2 >> 3)) break;
+    if (y - k >= 0) {
+      const ulonglong2 f = in[(long)v - (long)k * W];
+      if (f.x != PAIR_INF) keep_two(k1, k2, f.x + (c << 3));
+      if (f.y != PAIR_INF) keep_two(k1, k2, f.y + (c << 3));
+    }
+    if (y + k < H) {
+      const ulonglong2 f = in[(long)v + (long)k * W];
+      if (f.x != PAIR_INF) keep_two(k1, k2, f.x + (c << 3));
+      if (f.y != PAIR_INF) keep_two(k1, k2, f.y + (c << 3));
+    }
+  }
+  cap_two(k1, k2, cap2);
+  out[v] = make_ulonglong2(k1, k2);
+}
+
+// z pass of both transforms and the outputs.  d2 comes from line_min on the pleural work volume, the very code of
+// edt_z_kernel; f2 only asks for the voxel's own class, so its loop ends at (s k)^2 >= the best foreign distance so far,
+// and it is skipped outside the lung, and inside the peel when no distance volume is wanted (the peel wins).
+template <typename LT, typename T>
+__global__ __launch_bounds__(TPB) void lobe_z_kernel(const T* __restrict__ in, const ulonglong2* __restrict__ pairs,
+                                                     const LT* __restrict__ lab, long sz, long sy, int D, int H, int W,
+                                                     unsigned total, unsigned long long s, int K, unsigned long long cap2,
+                                                     unsigned long long peel2, unsigned long long fis2, int n_regions,
+                                                     uint8_t* __restrict__ zones, uint8_t* __restrict__ zone_labels,
+                                                     float* __restrict__ pleura_mm, float* __restrict__ fissure_mm) {
+  const unsigned v = blockIdx.x * (unsigned)TPB + threadIdx.x;
+  if (v >= total) return;
+  const unsigned plane = (unsigned)H * (unsigned)W;
+  const int z = (int)(v / plane);
+  const unsigned long long d2 = line_min<T>(in, (long)v, z, D, (long)plane, s, K, cap2);
+  const unsigned r = v - (unsigned)z * plane;
+  const int lb = (int)lab[z * sz + (long)(r / (unsigned)W) * sy + (long)(r % (unsigned)W)];
+  const unsigned cv = lb <= 0 ? 0u : (lb > n_regions ? (unsigned)n_regions + 1u : (unsigned)lb);
+  const bool lung = d2 != 0ull;
+  const bool peel = lung && d2 <= peel2;
+  unsigned long long f2 = ~0ull;
+  if (lung && (!peel || fissure_mm)) {
+    f2 = foreign(pairs[v], cv);
+    for (int k = 1; k <= K; ++k) {
+      const unsigned long long e = s * (unsigned long long)k, c = e * e;
+      if (c >= f2) break;
+      if (z - k >= 0) {
+        const unsigned long long f = foreign(pairs[(long)v - (long)k * plane], cv);
+        if (f != ~0ull) f2 = min(f2, f + c);
+      }
+      if (z + k < D) {
+        const unsigned long long f = foreign(pairs[(long)v + (long)k * plane], cv);
+        if (f != ~0ull) f2 = min(f2, f + c);
+      }
+    }
+    if (f2 > cap2) f2 = ~0ull;
+  }
+  const int zone = !lung ? 0 : (peel ? 1 : (f2 <= fis2 ? 3 : 2));
+  zones[v] = (uint8_t)zone;
+  if (zone_labels) zone_labels[v] = (uint8_t)(zone == 0 ? 0 : (lb > n_regions ? 255 : lb + n_regions * (zone - 1)));
+  if (pleura_mm)
+    pleura_mm[v] = d2 == ~0ull ? std::numeric_limits<float>::infinity() : (float)(sqrt((double)d2) / 1000.0);
+  if (fissure_mm)
+    fissure_mm[v] = !lung ? 0.0f
+                          : (f2 == ~0ull ? std::numeric_limits<float>::infinity() : (float)(sqrt((double)f2) / 1000.0));
+}
+
+template <typename LT, typename T>
+int run_lobe(const void* labels, long sz, long sy, uint8_t* zones, uint8_t* zone_labels, float* pleura_mm, float* fissure_mm,
+             void* workspace, int D, int H, int W, int sz_um, int sy_um, int sx_um, long long peel_um, long long fissure_um,
+             long long max_um, int n_regions, hipStream_t s) {
+  const long long total = (long long)D * H * W;
+  const long rows = (long)D * H;
+  T* a = (T*)workspace;
+  T* b = (T*)((char*)workspace + vol_bytes(total, (int)sizeof(T)));
+  ulonglong2* p = (ulonglong2*)((char*)workspace + 2 * vol_bytes(total, (int)sizeof(T)));
+  ulonglong2* q = (ulonglong2*)((char*)p + vol_bytes(total, 16));
+  const unsigned long long cap2 = (unsigned long long)max_um * (unsigned long long)max_um;
+  const unsigned long long peel2 = (unsigned long long)peel_um * (unsigned long long)peel_um;
+  const unsigned long long fis2 = (unsigned long long)fissure_um * (unsigned long long)fissure_um;
+  const int Kx = window(W, sx_um, max_um), Ky = window(H, sy_um, max_um), Kz = window(D, sz_um, max_um);
+  const unsigned vgrid = (unsigned)((total + TPB - 1) / TPB);
+  const double vox = (double)total, e = (double)sizeof(T), lb = (double)sizeof(LT);
+  {                                                             // the pleural x and y passes: dram_lung_zones' own
+    DramProf prof(DRAM_FAM_PREP, 13, 0.0, vox * (2.0 * lb + 3.0 * e), s);
+    hipLaunchKernelGGL((edt_x_kernel<LT, T>), dim3((unsigned)((rows + TPB / 64 - 1) / (TPB / 64))), dim3(TPB), 0, s,
+                       (const LT*)labels, sz, sy, H, W, rows, (unsigned long long)sx_um, (long long)Kx, a);
+    DRAM_LAUNCH_CHECK();
+  }
+  {
+    DramProf prof(DRAM_FAM_PREP, 14, 0.0, vox * 2.0 * e, s);
+    hipLaunchKernelGGL((edt_y_kernel<T>), dim3(vgrid), dim3(TPB), 0, s, (const T*)a, b, H, W, (unsigned)total,
+                       (unsigned long long)sy_um, Ky, cap2);
+    DRAM_LAUNCH_CHECK();
+  }
+  {
+    DramProf prof(DRAM_FAM_PREP, 22, 0.0, vox * (lb + 16.0), s);
+    hipLaunchKernelGGL((lobe_x_kernel<LT>), dim3(vgrid), dim3(TPB), 0, s, (const LT*)labels, sz, sy, H, W, (unsigned)total,
+                       (unsigned long long)sx_um, Kx, cap2, n_regions, p);
+    DRAM_LAUNCH_CHECK();
+  }
+  {
+    DramProf prof(DRAM_FAM_PREP, 23, 0.0, vox * 32.0, s);
+    hipLaunchKernelGGL(lobe_y_kernel, dim3(vgrid), dim3(TPB), 0, s, (const ulonglong2*)p, q, H, W, (unsigned)total,
+                       (unsigned long long)sy_um, Ky, cap2);
+    DRAM_LAUNCH_CHECK();
+  }
+  DramProf prof(DRAM_FAM_PREP, 24, 0.0,
+                vox * (e + 16.0 + lb + 1.0 + (zone_labels ? 1.0 : 0.0) + (pleura_mm ? 4.0 : 0.0) + (fissure_mm ? 4.0 : 0.0)), s);
+  hipLaunchKernelGGL((lobe_z_kernel<LT, T>), dim3(vgrid), dim3(TPB), 0, s, (const T*)b, (const ulonglong2*)q,
+                     (const LT*)labels, sz, sy, D, H, W, (unsigned)total, (unsigned long long)sz_um, Kz, cap2, peel2, fis2,
+                     n_regions, zones, zone_labels, pleura_mm, fissure_mm);
+  DRAM_LAUNCH_CHECK();
+  return DRAM_OK;
+}
+
 }  // namespace
+
+extern "C" long long dram_lobe_zones_workspace(int D, int H, int W, long long max_um) {
+  if (D < 1 || H < 1 || W < 1 || max_um < 0 || (long long)D * H * W >= (1LL << 31)) return 0;
+  const long long total = (long long)D * H * W;
+  return 2 * vol_bytes(total, max_um <= 65535 ? 4 : 8) + 2 * vol_bytes(total, 16);
+}
+
+extern "C" int dram_lobe_zones(const void* labels, int label_dtype, long long stride_z, long long stride_y, uint8_t* zones,
+                               uint8_t* zone_labels, float* pleura_mm, float* fissure_mm_out, void* workspace, int D, int H,
+                               int W, int sz_um, int sy_um, int sx_um, long long peel_um, long long fissure_um,
+                               long long max_um, int n_regions, dram_stream_t stream) {
+  if (!labels || !zones || !workspace || (label_dtype != 1 && label_dtype != 2) || stride_z < 0 || stride_y < 0 ||
+      peel_um < 0 || fissure_um < 0 || max_um < peel_um || max_um < fissure_um || n_regions < 1 || n_regions > 5)
+    return DRAM_ERR_BAD_ARG;
+  const int rc = check_sizes(D, H, W, sz_um, sy_um, sx_um);
+  if (rc != DRAM_OK) return rc;
+  if (max_um > FULL_UM) max_um = FULL_UM;
+  if (peel_um > FULL_UM) peel_um = FULL_UM;
+  if (fissure_um > FULL_UM) fissure_um = FULL_UM;
+  hipStream_t s = (hipStream_t)stream;
+  const long sz = (long)stride_z, sy = (long)stride_y;
+  if (max_um <= 65535)
+    return label_dtype == 1
+               ? run_lobe<uint8_t, uint32_t>(labels, sz, sy, zones, zone_labels, pleura_mm, fissure_mm_out, workspace, D, H, W,
+                                             sz_um, sy_um, sx_um, peel_um, fissure_um, max_um, n_regions, s)
+               : run_lobe<int16_t, uint32_t>(labels, sz, sy, zones, zone_labels, pleura_mm, fissure_mm_out, workspace, D, H, W,
+                                             sz_um, sy_um, sx_um, peel_um, fissure_um, max_um, n_regions, s);
+  return label_dtype == 1
+             ? run_lobe<uint8_t, uint64_t>(labels, sz, sy, zones, zone_labels, pleura_mm, fissure_mm_out, workspace, D, H, W,
+                                           sz_um, sy_um, sx_um, peel_um, fissure_um, max_um, n_regions, s)
+             : run_lobe<int16_t, uint64_t>(labels, sz, sy, zones, zone_labels, pleura_mm, fissure_mm_out, workspace, D, H, W,
+                                           sz_um, sy_um, sx_um, peel_um, fissure_um, max_um, n_regions, s);
+}
 
 extern "C" long long dram_lung_zones_workspace(int D, int H, int W, long long max_um) {
   if (D < 1 || H < 1 || W < 1 || max_um < 0 || (long long)D * H * W >= (1LL << 31)) return 0;

@@ -125,10 +125,11 @@ def _req(t: Tensor, name: str, dtype=torch.float32, shape=None):
 
 
 def _n_regions(fn: str, n_regions, hi: int = 15) -> int:
-    """n_regions as an int in 1..hi: 15 rows are what the region kernels hold, 7 what ``lung_zones`` can still double."""
+    """n_regions as an int in 1..hi: 15 rows are what the region kernels hold, 7 what ``lung_zones`` can still double,
+    5 what ``lobe_zones`` can still triple."""
     n = int(n_regions)
     if not 1 <= n <= hi:
-        note = " (2 n <= 15 rows downstream)" if hi == 7 else ""
+        note = {7: " (2 n <= 15 rows downstream)", 5: " (3 n <= 15 rows downstream)"}.get(hi, "")
         raise ValueError(f"{fn}: n_regions must be 1..{hi}{note}, got {n_regions}")
     return n
 
@@ -1409,28 +1410,28 @@ def lobe_histogram(image: Tensor, labels: Tensor, n_regions: int = 5, hu_lo: int
 EDT_FULL_UM = 1 << 26           # max_um from here on is the full transform (no distance in a supported volume reaches it)
 
 
-def lung_zones_units(spacing, peel_mm, max_mm=None):
+def lung_zones_units(spacing, peel_mm, max_mm=None, fn: str = "lung_zones"):
     """(spacing in whole micrometres (z, y, x), peel_um, max_um) of ``lung_zones``: round(mm * 1000), ``max_mm=None``
     -> peel_mm, ``inf`` (or anything from 2^26 um on) -> ``EDT_FULL_UM``.  ValueError for a spacing or peel_mm that is
-    not positive and finite, a spacing outside 1..20000 um, and max_mm < peel_mm.  Pure host code."""
+    not positive and finite, a spacing outside 1..20000 um, and max_mm < peel_mm, in the name of ``fn``.  Pure host code."""
     sp = [float(v) for v in spacing]
     if len(sp) != 3:
-        raise ValueError("lung_zones: spacing must have three entries (z, y, x)")
+        raise ValueError(f"{fn}: spacing must have three entries (z, y, x)")
     if not all(math.isfinite(v) and v > 0 for v in sp):
-        raise ValueError(f"lung_zones: spacing must be positive and finite, got {tuple(sp)}")
+        raise ValueError(f"{fn}: spacing must be positive and finite, got {tuple(sp)}")
     s_um = [int(round(v * 1000.0)) for v in sp]
     if not all(1 <= s <= 20000 for s in s_um):
-        raise ValueError(f"lung_zones: spacing must round to 1..20000 um per axis, got {tuple(sp)} mm")
+        raise ValueError(f"{fn}: spacing must round to 1..20000 um per axis, got {tuple(sp)} mm")
     peel = float(peel_mm)
     if not (math.isfinite(peel) and peel > 0):
-        raise ValueError(f"lung_zones: peel_mm must be positive and finite, got {peel_mm}")
+        raise ValueError(f"{fn}: peel_mm must be positive and finite, got {peel_mm}")
     peel_um = min(int(round(peel * 1000.0)), EDT_FULL_UM)
     if max_mm is None:
         max_um = peel_um
     else:
         mx = float(max_mm)
         if math.isnan(mx) or mx < peel:
-            raise ValueError(f"lung_zones: max_mm {max_mm} must be at least peel_mm {peel_mm}")
+            raise ValueError(f"{fn}: max_mm {max_mm} must be at least peel_mm {peel_mm}")
         max_um = EDT_FULL_UM if math.isinf(mx) else min(int(round(mx * 1000.0)), EDT_FULL_UM)
     return tuple(s_um), peel_um, max(max_um, peel_um)
 
@@ -1469,6 +1470,66 @@ def lung_zones(labels: Tensor, spacing, peel_mm: float, n_regions: Optional[int]
         _chk(_L().dram_lung_zones(_p(labels), code, sz, sy, _p(zones), _p(zlab), _p(dist), _p(work), D, H, W, *s_um,
                                   peel_um, max_um, n, _stream()), "dram_lung_zones")
     return zones, zlab, dist
+
+
+def lobe_zones_units(spacing, peel_mm, fissure_mm, max_mm=None):
+    """(spacing in whole micrometres (z, y, x), peel_um, fissure_um, max_um) of ``lobe_zones``: ``lung_zones_units``'
+    rounding; ``max_mm=None`` -> max(peel_mm, fissure_mm), ``inf`` -> ``EDT_FULL_UM``.  ValueError for what
+    ``lung_zones_units`` refuses, a fissure_mm that is not positive and finite, and max_mm below either width.  Pure
+    host code."""
+    s_um, peel_um, _ = lung_zones_units(spacing, peel_mm, fn="lobe_zones")
+    fis = float(fissure_mm)
+    if not (math.isfinite(fis) and fis > 0):
+        raise ValueError(f"lobe_zones: fissure_mm must be positive and finite, got {fissure_mm}")
+    fis_um = min(int(round(fis * 1000.0)), EDT_FULL_UM)
+    widest = max(peel_um, fis_um)
+    if max_mm is None:
+        max_um = widest
+    else:
+        mx = float(max_mm)
+        if math.isnan(mx) or mx < float(peel_mm) or mx < fis:
+            raise ValueError(f"lobe_zones: max_mm {max_mm} must be at least peel_mm {peel_mm} and fissure_mm {fissure_mm}")
+        max_um = EDT_FULL_UM if math.isinf(mx) else min(int(round(mx * 1000.0)), EDT_FULL_UM)
+    return s_um, peel_um, fis_um, max(max_um, widest)
+
+
+def lobe_zones(labels: Tensor, spacing, peel_mm: float, fissure_mm: float, n_regions: int = 5,
+               max_mm: Optional[float] = None, want_dist: bool = False):
+    """Peel / core / fissural rind of the lobes: ``lung_zones``' pleural distance d2 and, per lung voxel, the exact
+    squared distance f2 to the nearest voxel of ANOTHER lobe (csrc/edt.hip; definitions: INTEGRATION.md B7).
+
+    labels, spacing, peel_mm and the supported sizes as ``lung_zones``; ``n_regions`` = n in 1..5 (3 n <= 15).  A voxel's
+    class is its label in 1..n, n + 1 for a lung label above n, 0 for a label <= 0; only classes 1..n are sites of f2 (a
+    lung voxel that belongs to no region makes no fissure).  ``max_mm``: distances above it are +inf (None:
+    max(peel_mm, fissure_mm), the least work that decides the zones; inf: the full transforms).  ->
+    (zones, zone_labels, pleura_mm | None, fissure_mm | None):
+      zones uint8: 0 not lung, 1 peel (d2 <= peel_um^2, ``lung_zones``' zone 1 bit for bit: the peel wins), 3 fissural
+        rind (not peel and f2 <= fissure_um^2), 2 core (the rest);
+      zone_labels uint8: class r in 1..n -> r + n * (zone - 1) (1..n peel, n+1..2n core, 2n+1..3n fissural rind), class
+        n + 1 -> 255 -- the label volume of ``lobe_histogram`` / ``upproject_regions`` with 3 n regions;
+      pleura_mm, fissure_mm float32 (``want_dist``): sqrt(d2 | f2) / 1000, 0 outside the lung, +inf where the squared
+        distance is (no background / no foreign site, or none within max_mm).
+    ``fissure_mm`` is the caller's choice.  Exact integers: bit-identical from call to call; never synchronises; every
+    check runs before any launch."""
+    s_um, peel_um, fis_um, max_um = lobe_zones_units(spacing, peel_mm, fissure_mm, max_mm)
+    n = _n_regions("lobe_zones", n_regions, 5)
+    if isinstance(labels, Tensor) and labels.dim() == 3:               # anything else: _label_view's refusal below
+        for size, s, axis in zip(labels.shape, s_um, "zyx"):
+            if (size - 1) * s >= 2 ** 25:
+                raise ValueError(f"lobe_zones: axis {axis}: (size - 1) * spacing = {(size - 1) * s} um must be below 2^25")
+    labels, code, sz, sy = _label_view("lobe_zones", labels, "labels")
+    D, H, W = (int(v) for v in labels.shape)
+    dev = labels.device
+    with launch_scope(dev):
+        nbytes = int(_L().dram_lobe_zones_workspace(D, H, W, max_um))
+        work = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+        zones = torch.empty((D, H, W), device=dev, dtype=torch.uint8)
+        zlab = torch.empty((D, H, W), device=dev, dtype=torch.uint8)
+        pleura = torch.empty((D, H, W), device=dev, dtype=torch.float32) if want_dist else None
+        fissure = torch.empty((D, H, W), device=dev, dtype=torch.float32) if want_dist else None
+        _chk(_L().dram_lobe_zones(_p(labels), code, sz, sy, _p(zones), _p(zlab), _p(pleura), _p(fissure), _p(work), D, H, W,
+                                  *s_um, peel_um, fis_um, max_um, n, _stream()), "dram_lobe_zones")
+    return zones, zlab, pleura, fissure
 
 
 CCL_TABLE_COLS = 35             # 32 size bins (2^k <= size < 2^(k+1)), components, foreground voxels, largest size

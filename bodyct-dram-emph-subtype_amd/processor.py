@@ -199,12 +199,13 @@ def densitometry_metrics(result: dict, names=None) -> dict:
 
 # --------------------------------------------------------------------------- core / peel split of the per-lobe report
 ZONES = ("peel", "core")
+FISSURE_ZONES = ("peel", "core", "fissure")          # with ``fissure_mm``: 'core' is then neither rind
 _CORE_PEEL_KEY = re.compile(r"((laa\d+_fraction|perc\d+_hu|mean_lung_density|volume_ml|(cle|pse)_lesion_percentage)"
-                            r"_per_(region|lung)|region_voxels)_(peel|core)|peel_mm")
+                            r"_per_(region|lung)|region_voxels)_(peel|core|fissure)|peel_mm|fissure_mm")
 
 
 def core_peel(image: torch.Tensor, labels: torch.Tensor, spacing: Sequence[float], peel_mm: float = 10.0,
-              n_regions: int = 5, **densitometry_kw) -> dict:
+              n_regions: int = 5, fissure_mm: Optional[float] = None, **densitometry_kw) -> dict:
     """``densitometry`` of every lobe split into its subpleural rind (the "peel": lung voxels within ``peel_mm`` of the
     nearest non-lung voxel of the crop, Euclidean, at the scan's own spacing) and the rest (the "core"):
     ``ops.lung_zones`` -> composite labels (1..n the peel, n+1..2n the core of lobe r) -> ONE ``ops.lobe_histogram``
@@ -214,57 +215,88 @@ def core_peel(image: torch.Tensor, labels: torch.Tensor, spacing: Sequence[float
       {'peel': <densitometry result>, 'core': <densitometry result>, 'outside_voxels': int64 0-dim (lung voxels whose
        label is above n_regions: row 0 of the composite histogram, in neither zone's rows), 'zones', 'zone_labels'
        (uint8 [D,H,W], ``ops.lung_zones``), 'peel_mm', 'n_regions'}.
-    The field of view is no pleura: a lung cut by the crop has no peel there.  Device tensors, nothing read back."""
+    The field of view is no pleura: a lung cut by the crop has no peel there.  Device tensors, nothing read back.
+
+    ``fissure_mm`` (None: off, everything above holds unchanged): a third zone, the fissural rind -- lung voxels outside
+    the peel within ``fissure_mm`` of the nearest voxel of ANOTHER lobe (labels 1..n; the pleura folds into the
+    interlobar fissures, which hold no non-lung voxel).  ``ops.lobe_zones`` -> composite labels (2n+1..3n the fissural
+    rind of lobe r) -> ONE ``ops.lobe_histogram`` with 3n rows; ``n_regions`` 1..5.  The result also holds 'fissure' (a
+    third densitometry result), 'fissure_mm' and 'zone_names' = ('peel', 'core', 'fissure'); 'peel' is what it is without
+    the argument, and 'core' then means NEITHER rind: the lung outside the peel and outside the fissural rind.
+    ``fissure_mm`` is the caller's choice as well."""
     n = int(n_regions)
     if not isinstance(image, torch.Tensor) or not isinstance(labels, torch.Tensor) or tuple(image.shape) != tuple(labels.shape):
         raise ValueError("core_peel: image and labels must be tensors of one [D,H,W] shape")
     kw = dict(densitometry_kw)
     hu_lo, nbins = int(kw.pop("hu_lo", -1024)), int(kw.pop("nbins", 1024))
-    zones, zone_labels, _ = ops.lung_zones(labels, spacing, peel_mm, n_regions=n)
-    hist, sums = ops.lobe_histogram(image, zone_labels, 2 * n, hu_lo, nbins)
+    names = ZONES if fissure_mm is None else FISSURE_ZONES
+    if fissure_mm is None:
+        zones, zone_labels, _ = ops.lung_zones(labels, spacing, peel_mm, n_regions=n)
+    else:
+        zones, zone_labels, _, _ = ops.lobe_zones(labels, spacing, peel_mm, fissure_mm, n_regions=n)
+    hist, sums = ops.lobe_histogram(image, zone_labels, len(names) * n, hu_lo, nbins)
     out = {}
-    for i, zone in enumerate(ZONES):
+    for i, zone in enumerate(names):
         rows = slice(1 + i * n, 1 + (i + 1) * n)
         out[zone] = densitometry_from_hist(torch.cat([torch.zeros_like(hist[:1]), hist[rows]]),
                                            torch.cat([torch.zeros_like(sums[:1]), sums[rows]]), spacing, hu_lo=hu_lo, **kw)
     out.update(outside_voxels=sums[0, 0], zones=zones, zone_labels=zone_labels, peel_mm=float(peel_mm), n_regions=n)
+    if fissure_mm is not None:
+        out.update(fissure_mm=float(fissure_mm), zone_names=FISSURE_ZONES)
     return out
 
 
 def core_peel_metrics(result: dict, names=None) -> dict:
     """``core_peel``'s result -> entries of the metrics dict: ``densitometry_metrics`` of each zone with the zone's name
     appended to every key ('laa950_fraction_per_region_peel', 'volume_ml_per_lung_core', ...: the same formats, keyed
-    through ``names`` the same way, None for NaN), and 'peel_mm' ("{:.3f}").  Pure host code."""
+    through ``names`` the same way, None for NaN), and 'peel_mm' ("{:.3f}").  The zones are those the result names
+    ('zone_names'; without it 'peel' and 'core'): a result of ``core_peel(fissure_mm=...)`` adds the keys ending
+    '_fissure' and 'fissure_mm' ("{:.3f}").  Pure host code."""
     out = {}
-    for zone in ZONES:
+    for zone in result.get("zone_names", ZONES):
         out.update({f"{k}_{zone}": v for k, v in densitometry_metrics(result[zone], names).items()})
     out["peel_mm"] = "{:.3f}".format(float(result["peel_mm"]))
+    if "fissure_mm" in result:
+        out["fissure_mm"] = "{:.3f}".format(float(result["fissure_mm"]))
     return out
 
 
-def fold_zone_table(table_row) -> torch.Tensor:
+def fold_zone_table(table_row, n_zones: int = 2) -> torch.Tensor:
     """The composite region table [2n+1, 4] (rows 1..n peel, n+1..2n core) -> the per-lobe one [n+1, 4] that
-    ``region_metrics`` reads, in float64 on the host: row r = row r + row n+r, row 0 stays row 0."""
+    ``region_metrics`` reads, in float64 on the host: row r = row r + row n+r, row 0 stays row 0.  ``n_zones`` = 3: the
+    table is [3n+1, 4] (2n+1..3n the fissural rind) and row r = row r + row n+r + row 2n+r, added in that order."""
     t = torch.as_tensor(table_row).detach().cpu().double()
-    if t.dim() != 2 or t.shape[1] != 4 or t.shape[0] < 3 or t.shape[0] % 2 != 1:
-        raise ValueError("fold_zone_table: table_row must be [2 * n_regions + 1, 4]")
-    n = (t.shape[0] - 1) // 2
-    return torch.cat([t[:1], t[1:n + 1] + t[n + 1:]])
+    z = int(n_zones)
+    if z not in (2, 3):
+        raise ValueError(f"fold_zone_table: n_zones must be 2 or 3, got {n_zones}")
+    if t.dim() != 2 or t.shape[1] != 4 or t.shape[0] < z + 1 or t.shape[0] % z != 1:
+        raise ValueError(f"fold_zone_table: table_row must be [{z} * n_regions + 1, 4]")
+    n = (t.shape[0] - 1) // z
+    rows = t[1:n + 1] + t[n + 1:2 * n + 1]
+    if z == 3:
+        rows = rows + t[2 * n + 1:]
+    return torch.cat([t[:1], rows])
 
 
-def zone_region_metrics(table_row, names=None) -> dict:
+def zone_region_metrics(table_row, names=None, zones=ZONES) -> dict:
     """One sample's composite region table [2n+1, 4] (predict_step's 'region_table'[b] for ``core_peel``'s zone labels
     and 'n_regions' = 2n) -> for each zone Z in ('peel', 'core') 'cle_lesion_percentage_per_region_Z',
     'pse_lesion_percentage_per_region_Z' and 'region_voxels_Z' (keyed and formatted like ``region_metrics``; None for
     a lobe without voxels in that zone) and 'cle_lesion_percentage_per_lung_Z' / 'pse_lesion_percentage_per_lung_Z' =
     sum / voxels over the zone's rows (None for an empty zone).  No severity scores: the ratio bands are defined per
-    lung.  Pure host code, float64."""
+    lung.  ``zones``: the zone names in the order of the table's row blocks -- ``FISSURE_ZONES`` for the [3n+1, 4] table
+    of ``core_peel(fissure_mm=...)``'s labels, which adds the keys ending '_fissure'; the row count alone does not tell
+    (7 rows are 3 lobes in two zones or 2 lobes in three).  Pure host code, float64."""
     rows = table_row.tolist() if torch.is_tensor(table_row) else [list(r) for r in table_row]
-    if len(rows) < 3 or len(rows) % 2 != 1 or any(len(r) != 4 for r in rows):
-        raise ValueError("zone_region_metrics: table_row must be [2 * n_regions + 1, 4]")
-    n = (len(rows) - 1) // 2
+    zones = tuple(zones)
+    z = len(zones)
+    if z not in (2, 3):
+        raise ValueError(f"zone_region_metrics: zones must name 2 or 3 zones, got {zones}")
+    if len(rows) < z + 1 or len(rows) % z != 1 or any(len(r) != 4 for r in rows):
+        raise ValueError(f"zone_region_metrics: table_row must be [{z} * n_regions + 1, 4]")
+    n = (len(rows) - 1) // z
     out = {}
-    for i, zone in enumerate(ZONES):
+    for i, zone in enumerate(zones):
         per = {f"{h}_lesion_percentage_per_region_{zone}": {} for h in ("cle", "pse")}
         per[f"region_voxels_{zone}"] = {}
         tot = [0.0, 0.0, 0.0]
@@ -446,7 +478,8 @@ def build_outputs(predictions: List[dict], want_u8: bool = True, region_names=No
 def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Sequence[float], target_size: Sequence[int],
                  uid=None, want_u8: bool = True, regions: bool = False, region_names=None, densitometry: bool = False,
                  densitometry_kw: Optional[dict] = None, core_peel: bool = False, peel_mm: float = 10.0,
-                 clusters: bool = False, cluster_kw: Optional[dict] = None, scan_filter=None,
+                 fissure_mm: Optional[float] = None, clusters: bool = False, cluster_kw: Optional[dict] = None,
+                 scan_filter=None,
                  scan_filter_sections: Sequence[str] = ("densitometry", "core_peel", "clusters"), **prepare_kw) -> dict:
     """One scan + its lobe segmentation -> its entry of ``build_outputs``: ``transforms.prepare_case`` (dataset.py:57-92)
     -> ``transforms.prepare_sample(target_size)`` -> a batch of one -> ``module.predict_step`` -> ``build_outputs``.
@@ -465,6 +498,12 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     tail gives a [2n+1, 4] table, and the entry carries ``zone_region_metrics`` of it; with ``regions`` the table
     ``region_metrics`` reads is that one folded on the host (``fold_zone_table``).  A line in error_messages when lung
     voxels carry a label above n_regions.
+
+    ``fissure_mm`` (None: off; needs ``core_peel`` and the module's n_regions <= 5, else ValueError before any device
+    work): the section gains a third zone, the fissural rind of ``core_peel(fissure_mm=...)`` -- voxels outside the peel
+    within ``fissure_mm`` (the caller's choice) of another lobe.  The composite labels travel with 'n_regions' = 3n,
+    the one fused tail gives a [3n+1, 4] table, every zone key gains a twin ending '_fissure', and the entry carries
+    'fissure_mm'; the keys ending '_core' then describe the lung in neither rind.
 
     ``clusters`` (independent of the three): the entry also carries ``laa_cluster_metrics`` of ``laa_clusters`` on the
     case's 'image' and 'lobe_labels' before the resize (``cluster_kw``: n_regions, threshold, connectivity), keyed
@@ -494,9 +533,17 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     on = {"regions": bool(regions), "densitometry": bool(densitometry), "core_peel": bool(core_peel),
           "clusters": bool(clusters)}
     kw = {"densitometry": dict(densitometry_kw or {}), "clusters": dict(cluster_kw or {})}
+    if fissure_mm is not None and not core_peel:
+        raise ValueError("predict_case: fissure_mm adds the fissural rind to the core / peel section: it needs "
+                         "core_peel=True")
     if core_peel:
         n = int(getattr(module.args, "n_regions", 5))
         kw["core_peel"] = dict(densitometry_kw or {}, peel_mm=peel_mm)
+        if fissure_mm is not None:
+            if not 1 <= n <= 5:
+                raise ValueError(f"predict_case: fissure_mm splits every lobe in three (3 n <= 15 rows downstream): the "
+                                 f"module's n_regions = {n} must be 1..5")
+            kw["core_peel"]["fissure_mm"] = fissure_mm
         if int(kw["core_peel"].setdefault("n_regions", n)) != n:
             raise ValueError(f"predict_case: core_peel splits the module's n_regions = {n} lobes; densitometry_kw asks "
                              "for another count")
@@ -508,6 +555,8 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
                for name in _LAUNCH_ORDER if on[name]}
     cp = results.get("core_peel")
     # core / peel rides the network side on the regions' tail: its zone labels are the batch's labels, with 2n regions
+    # (3n with the fissural rind)
+    zone_names = ZONES if cp is None else cp.get("zone_names", ZONES)
     if cp is not None:
         case = dict(case, lobe_labels=cp["zone_labels"])
     elif not regions:
@@ -518,14 +567,14 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     batch = {k: sample[k].unsqueeze(0) for k in keys}
     batch["uid"] = [uid]
     if cp is not None:
-        batch["n_regions"] = 2 * cp["n_regions"]
+        batch["n_regions"] = len(zone_names) * cp["n_regions"]
     pred = module.predict_step(batch, 0)
     if cp is not None:
         composite = pred["region_table"][0].cpu()
-        results["core_peel"] = dict(cp, zone_metrics=zone_region_metrics(composite, region_names))
+        results["core_peel"] = dict(cp, zone_metrics=zone_region_metrics(composite, region_names, zone_names))
         pred = {k: v for k, v in pred.items() if k != "region_table"}
         if regions:
-            pred["region_table"] = fold_zone_table(composite).unsqueeze(0)
+            pred["region_table"] = fold_zone_table(composite, len(zone_names)).unsqueeze(0)
     entry = build_outputs([pred], want_u8=want_u8, region_names=region_names)[0]
     for name, section in _SECTIONS.items():
         if name in results:

@@ -739,6 +739,37 @@ int dram_lung_zones(const void* labels, int label_dtype, long long stride_z, lon
                     uint8_t* zone_labels, float* dist_mm, void* workspace, int D, int H, int W, int sz_um, int sy_um,
                     int sx_um, long long peel_um, long long max_um, int n_regions, dram_stream_t stream);
 
+/* Peel / core / fissural rind of the lobes from two exact distance transforms (csrc/edt.hip; definitions:
+ * INTEGRATION.md B7).  labels, strides, spacings, d2, peel_um, max_um and the supported sizes are dram_lung_zones'.
+ * With n = n_regions in 1..5 (3 n <= 15), the class of a voxel is its label for a label in 1..n, n + 1 for a lung label
+ * above n and 0 for a label <= 0; a SITE is a voxel of class 1..n (a lung voxel that belongs to no region makes no
+ * fissure), and per lung voxel
+ *   f2(v) = min over sites u with class(u) != class(v) of sum_a (s_a (v_a - u_a))^2   [um^2, to the centre of u],
+ * +inf when there is no such site or none within max_um (f2 > max_um^2); a voxel beside a foreign one has f2 = s_a^2.
+ *   zones [D,H,W] uint8: 0 not lung, 1 peel (d2 <= peel_um^2: bit for bit dram_lung_zones' zone 1 -- the peel wins),
+ *     3 fissural rind (not peel and f2 <= fissure_um^2, equality included), 2 core (the rest, +inf included); zones
+ *     2 and 3 together are dram_lung_zones' zone 2;
+ *   zone_labels [D,H,W] uint8, optional (NULL): 0 not lung; class r in 1..n -> r + n * (zone - 1), so 1..n is the peel,
+ *     n+1..2n the core and 2n+1..3n the fissural rind of region r; class n + 1 -> 255 (row 0 of dram_lobe_hist /
+ *     dram_upproject_regions called with 3 n regions);
+ *   pleura_mm, fissure_mm_out [D,H,W] float32, optional (NULL): float(sqrt(double(d2 | f2)) / 1000.0), 0 outside the
+ *     lung, +inf with the squared distance;
+ *   workspace: dram_lobe_zones_workspace(D, H, W, max_um) bytes (dram_lung_zones' two work volumes, then two of 16-byte
+ *     elements: the two nearest sites of distinct classes as (d2 << 3) | class; 0 for sizes the call refuses), 256-byte
+ *     aligned, owned by the caller; needs no clearing.
+ * Five launches (the pleural x and y passes -- dram_lung_zones' own kernels --, the x and y passes of the pairs, one z
+ * pass of both with the outputs); every output element and every workspace element that is read is written by them.
+ * No global atomics, no ticket word, no waiting between workgroups, never synchronises, capturable; integer minima:
+ * bit-identical from call to call.
+ * Null labels / zones / workspace, label_dtype not 1 / 2, a size < 1, a negative stride, peel_um < 0, fissure_um < 0,
+ * max_um below either width, n_regions outside 1..5: DRAM_ERR_BAD_ARG.  Sizes and spacings outside dram_lung_zones'
+ * support: DRAM_ERR_UNSUPPORTED. */
+long long dram_lobe_zones_workspace(int D, int H, int W, long long max_um);
+int dram_lobe_zones(const void* labels, int label_dtype, long long stride_z, long long stride_y, uint8_t* zones,
+                    uint8_t* zone_labels, float* pleura_mm, float* fissure_mm_out, void* workspace, int D, int H, int W,
+                    int sz_um, int sy_um, int sx_um, long long peel_um, long long fissure_um, long long max_um,
+                    int n_regions, dram_stream_t stream);
+
 /* Connected-component labelling of a 3-D key volume and the per-row cluster table of the LAA cluster analysis
  * (csrc/ccl.hip; definitions: INTEGRATION.md B8).  A key is a non-negative integer per voxel, 0 is background; two
  * voxels are connected when they are neighbours under `connectivity` (6: faces; 26: faces, edges, corners) and carry the
