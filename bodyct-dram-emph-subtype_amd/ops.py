@@ -1595,6 +1595,74 @@ def laa_components(image: Tensor, labels: Tensor, threshold: int = -950, n_regio
                              n_regions if by_lobe else 1, want_sizes)
 
 
+SHAPE_COLS = 18                 # columns of a ``component_shapes`` row
+SHAPE_ROOT, SHAPE_CLASS, SHAPE_VOXELS = 0, 1, 2
+SHAPE_Z0, SHAPE_Z1, SHAPE_Y0, SHAPE_Y1, SHAPE_X0, SHAPE_X1 = 3, 4, 5, 6, 7, 8     # bounding box, half-open
+SHAPE_SUM_Z, SHAPE_SUM_Y, SHAPE_SUM_X = 9, 10, 11                                   # the centroid's numerators
+SHAPE_FACES_Z, SHAPE_FACES_Y, SHAPE_FACES_X = 12, 13, 14                            # exposed faces normal to the axis
+SHAPE_ZONE1, SHAPE_ZONE2, SHAPE_ZONE3 = 15, 16, 17                                  # voxels with zones == 1, 2, 3
+
+
+def component_shapes(components: Tensor, labels: Optional[Tensor] = None, zones: Optional[Tensor] = None,
+                     max_components: Optional[int] = None):
+    """One row per connected component of a labelled volume (csrc/ccl_shapes.hip; definitions: INTEGRATION.md B8).
+
+    components [D,H,W] int32, contiguous, only read: ``label_components``' first output, the linear index of the
+    component's smallest voxel, -1 on background.  A voxel v with c = components[v] counts in component c only when
+    0 <= c < D*H*W and components[c] == c; any other voxel is background.  labels (optional) [D,H,W] uint8 / int16 /
+    bool, a view as ``label_components`` takes it; zones (optional) [D,H,W] uint8, contiguous: ``lung_zones`` /
+    ``lobe_zones``' first output.  -> (rows, count):
+      rows int64 [m, 18], row r the component whose root (``components[v] == v``) is the r-th in ascending linear index;
+        columns (``SHAPE_*``): 0 root, 1 class (labels at the root, 0 without labels), 2 voxels, 3..8 z0, z1, y0, y1, x0,
+        x1 (half-open box), 9..11 the sums of z, y, x over the voxels, 12..14 the exposed faces normal to z, y, x (the
+        neighbour along the axis lies outside the volume or holds another value in ``components``; two components that
+        touch each count the shared face), 15..17 the voxels with zones == 1, 2, 3 (0 without zones);
+      count int64 [2]: the number of components, and the rows filled = min(that, m).
+    ``max_components=None``: m is the number of components -- ``count[0]`` is read back between the ranking and the
+    accumulation, the ONE synchronisation of this call; an empty volume gives zero rows.  ``max_components=k``: nothing
+    is read back, rows is [k, 18], truncated to the first k components or zero-padded, and the caller reads ``count``.
+    Fewer than 2^31 voxels.  Integer atomics only: bit-identical from call to call; every check runs before any
+    launch."""
+    fn = "component_shapes"
+    if not isinstance(components, Tensor) or components.dim() != 3 or min(components.shape) < 1:
+        raise ValueError(f"{fn}: components must be a non-empty [D,H,W] tensor")
+    if components.dtype != torch.int32:
+        raise TypeError(f"{fn}: expected int32 components, got {components.dtype}")
+    if components.numel() >= 2 ** 31:
+        raise ValueError(f"{fn}: volumes of 2^31 voxels or more are not supported")
+    D, H, W = (int(v) for v in components.shape)
+    if zones is not None:
+        if not isinstance(zones, Tensor) or zones.dtype != torch.uint8:
+            raise TypeError(f"{fn}: zones must be a uint8 tensor")
+        if tuple(zones.shape) != (D, H, W):
+            raise ValueError(f"{fn}: zones {tuple(zones.shape)} must have the shape of components {(D, H, W)}")
+    cap = None
+    if max_components is not None:
+        cap = int(max_components)
+        if cap != max_components or cap < 0:
+            raise ValueError(f"{fn}: max_components must be a non-negative integer, got {max_components}")
+    code, sz, sy = 1, 0, 0
+    if labels is not None:
+        labels, code, sz, sy = _label_view(fn, labels, "labels", (D, H, W))
+    dev = components.device
+    with launch_scope(dev):
+        _req(components, f"{fn}: components", torch.int32)
+        if zones is not None:
+            _req(zones, f"{fn}: zones", torch.uint8)
+        if labels is not None and labels.device != dev:
+            raise RuntimeError(f"{fn}: labels must live on the device of components")
+        work = torch.empty((int(_L().dram_component_shapes_workspace(D, H, W)),), device=dev, dtype=torch.uint8)
+        count = torch.empty((2,), device=dev, dtype=torch.int64)
+        _chk(_L().dram_component_rank(_p(components), _p(work), _p(count), D, H, W, _stream()), "dram_component_rank")
+        if cap is None:
+            cap = int(count[0].item())                                 # the one synchronisation
+        rows = torch.empty((cap, SHAPE_COLS), device=dev, dtype=torch.int64)
+        _chk(_L().dram_component_shapes(_p(components), _p(labels), code, sz, sy, _p(zones), _p(work),
+                                        _p(rows) if cap else None, cap, _p(count), D, H, W, _stream()),
+             "dram_component_shapes")
+    return rows, count
+
+
 def median_size(fn: str, size) -> Tuple[int, int, int]:
     """A median window ``size`` -- three entries in (z, y, x) order, each 1 or 3, at least one 3 -- as a tuple of ints;
     ValueError for anything else.  Pure host code."""

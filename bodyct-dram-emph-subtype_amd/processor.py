@@ -314,7 +314,9 @@ def zone_region_metrics(table_row, names=None, zones=ZONES) -> dict:
 
 
 # --------------------------------------------------------------------------- LAA cluster analysis per lobe
-_CLUSTER_KEY = re.compile(r"laa\d+_(clusters|largest_cluster_ml|cluster_d)_per_(region|lung)|laa_cluster_connectivity")
+_CLUSTER_KEY = re.compile(r"laa\d+_(clusters|largest_cluster_ml|cluster_d|bullae|bulla_ml|bulla_laa_share)_per_(region|lung)"
+                          r"|laa\d+_(clusters|bullae)_per_(region|lung)_(peel|core|fissure)|laa\d+_largest_clusters"
+                          r"|laa_cluster_connectivity|bulla_mm|bulla_min_voxels")
 
 
 def clusters_from_table(table: torch.Tensor, spacing: Sequence[float]) -> dict:
@@ -356,20 +358,159 @@ def clusters_from_table(table: torch.Tensor, spacing: Sequence[float]) -> dict:
             "mean_voxels": mean_vox, "size_hist": hist, "d": d}
 
 
+def bulla_min_voxels(spacing: Sequence[float], bulla_mm: float) -> int:
+    """The smallest cluster, in voxels, whose equivalent-sphere diameter reaches ``bulla_mm``:
+    max(1, ceil(pi/6 * bulla_mm^3 / (sz*sy*sx))), float64 on the host."""
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
+        raise ValueError("bulla_min_voxels: spacing must have three positive, finite entries (z, y, x)")
+    mm = float(bulla_mm)
+    if not (math.isfinite(mm) and mm > 0):
+        raise ValueError(f"bulla_min_voxels: bulla_mm must be positive and finite, got {bulla_mm}")
+    return max(1, int(math.ceil(math.pi / 6.0 * mm ** 3 / (sp[0] * sp[1] * sp[2]))))
+
+
+def shapes_from_rows(rows: torch.Tensor, spacing: Sequence[float], n_regions: int, bulla_mm: float = 10.0, top: int = 3,
+                     origin: Sequence[int] = (0, 0, 0), n_zones: int = 0) -> dict:
+    """The tensor math of the cluster shapes: ``ops.component_shapes``' rows int64 [m, 18] (m = 0 is valid) -> a dict.
+
+    Scalars: 'bulla_mm' and 'bulla_min_voxels' (``bulla_min_voxels(spacing, bulla_mm)``, an int computed once on the
+    host).  A cluster is a BULLA when its voxels >= bulla_min_voxels -- an integer comparison, hence exact; it says
+    "equivalent-sphere diameter at least ``bulla_mm``".  The 10 mm default is the common definition; it is the caller's
+    choice and no recommendation.
+    Per row 0..n_regions (a cluster's class r in 1..n -> row r, any other class -> row 0): 'bullae', 'bulla_voxels',
+    'cluster_voxels' (int64), 'bulla_ml' (float64) and 'bulla_laa_share' = bulla voxels / the row's cluster voxels
+    (float64, NaN for a row without clusters).
+    Per cluster, in the order of the rows: 'region' (its row, int64), 'voxels', 'is_bulla', 'volume_ml', 'diameter_mm' =
+    (6 V / pi)^(1/3), 'extent_mm' [m, 3] = box * spacing, 'centroid' [m, 3] = sums / voxels + origin (voxels of the grid
+    the origin is given in, (z, y, x)), 'surface_mm2' = fz sy sx + fy sz sx + fx sz sy, 'sphericity' = pi^(1/3)
+    (6 V)^(2/3) / surface, and 'home_zone' (int64): the zone 1..3 that holds most of its voxels, the lower zone on a
+    tie, 0 when the three counts are 0.  The surface is a sum of voxel faces, which overstates a smooth surface by a
+    factor that depends on orientation: a cube has sphericity 0.806, a voxelised ball about 2/3 -- the number compares
+    clusters of one report with each other and with nothing else.
+    With ``n_zones`` = 2 or 3 (the rows were made with a zone volume): 'zone_clusters' and 'zone_bullae' int64
+    [n_regions + 1, n_zones], the clusters / bullae of a row by home zone (a home zone of 0 or above n_zones counts in
+    neither).
+    'largest': the indices (int64 [min(top, m)]) of the ``top`` clusters by voxels descending, root ascending on ties.
+    int64 / float64 torch operations on the rows' own device (CPU tensors work), nothing read back."""
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype != torch.int64 or rows.shape[1] != ops.SHAPE_COLS:
+        raise ValueError(f"shapes_from_rows: rows must be int64 [m, {ops.SHAPE_COLS}]")
+    n, nz, k = int(n_regions), int(n_zones), int(top)
+    if n < 1 or nz not in (0, 2, 3) or k < 0:
+        raise ValueError("shapes_from_rows: n_regions >= 1, n_zones 0, 2 or 3 and top >= 0 are required")
+    sp = [float(v) for v in spacing]
+    org = [int(v) for v in origin]
+    if len(org) != 3:
+        raise ValueError("shapes_from_rows: origin must have three entries (z, y, x)")
+    need = bulla_min_voxels(sp, bulla_mm)
+    dev, f64 = rows.device, torch.float64
+    voxel = sp[0] * sp[1] * sp[2]
+    cls, vox = rows[:, ops.SHAPE_CLASS], rows[:, ops.SHAPE_VOXELS]
+    region = torch.where((cls >= 1) & (cls <= n), cls, torch.zeros_like(cls))
+    is_bulla = vox >= need
+    zero = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    per_row = lambda w: zero.index_add(0, region, w)
+    bullae, bulla_vox, cluster_vox = per_row(is_bulla.long()), per_row(vox * is_bulla.long()), per_row(vox)
+    share = torch.where(cluster_vox > 0, bulla_vox.double() / cluster_vox.clamp_min(1).double(),
+                        torch.full((n + 1,), float("nan"), dtype=f64, device=dev))
+    v_mm3 = vox.double() * voxel
+    box = rows[:, ops.SHAPE_Z0:ops.SHAPE_X1 + 1].reshape(-1, 3, 2)
+    spt = torch.tensor(sp, dtype=f64, device=dev)
+    extent = (box[:, :, 1] - box[:, :, 0]).double() * spt
+    centroid = rows[:, ops.SHAPE_SUM_Z:ops.SHAPE_SUM_X + 1].double() / vox.clamp_min(1).double()[:, None] + \
+        torch.tensor(org, dtype=f64, device=dev)
+    faces = rows[:, ops.SHAPE_FACES_Z:ops.SHAPE_FACES_X + 1].double()
+    surface = faces[:, 0] * (sp[1] * sp[2]) + faces[:, 1] * (sp[0] * sp[2]) + faces[:, 2] * (sp[0] * sp[1])
+    sphericity = math.pi ** (1.0 / 3.0) * (6.0 * v_mm3) ** (2.0 / 3.0) / surface
+    zc = rows[:, ops.SHAPE_ZONE1:ops.SHAPE_ZONE3 + 1]
+    best = zc.amax(1)
+    ties = (zc == best[:, None]).long()
+    first = 2 - ties[:, 0] * 2 - (1 - ties[:, 0]) * ties[:, 1]                        # the lowest zone among the maxima
+    home = torch.where(best > 0, first + 1, torch.zeros_like(best))
+    out = {"bulla_mm": float(bulla_mm), "bulla_min_voxels": need, "bullae": bullae, "bulla_voxels": bulla_vox,
+           "cluster_voxels": cluster_vox, "bulla_ml": bulla_vox.double() * voxel / 1000.0, "bulla_laa_share": share,
+           "region": region, "voxels": vox, "is_bulla": is_bulla, "volume_ml": v_mm3 / 1000.0,
+           "diameter_mm": (6.0 * v_mm3 / math.pi) ** (1.0 / 3.0), "extent_mm": extent, "centroid": centroid,
+           "surface_mm2": surface, "sphericity": sphericity, "home_zone": home}
+    if nz:
+        flat = torch.zeros((n + 1) * nz, dtype=torch.int64, device=dev)
+        zoned = ((home >= 1) & (home <= nz)).long()
+        slot = region * nz + (home - 1).clamp(0, nz - 1)
+        out["zone_clusters"] = flat.index_add(0, slot, zoned).reshape(n + 1, nz)
+        out["zone_bullae"] = flat.index_add(0, slot, zoned * is_bulla.long()).reshape(n + 1, nz)
+    out["largest"] = torch.sort(vox, descending=True, stable=True)[1][:k]
+    return out
+
+
 def laa_clusters(image: torch.Tensor, labels: torch.Tensor, spacing: Sequence[float], n_regions: int = 5,
-                 threshold: int = -950, connectivity: int = 6) -> dict:
+                 threshold: int = -950, connectivity: int = 6, shapes: bool = False, bulla_mm: float = 10.0, top: int = 3,
+                 zones: Optional[torch.Tensor] = None, zone_names: Optional[Sequence[str]] = None,
+                 origin: Sequence[int] = (0, 0, 0)) -> dict:
     """How the low attenuation of every lobe is arranged: the connected clusters of ``image <
     threshold`` inside each lobe (``ops.laa_components(by_lobe=True)``: a cluster never crosses a fissure) ->
     ``clusters_from_table`` for the rows 0..n_regions (row 0: LAA voxels whose label is above n_regions), and once more
     over the whole lung (``by_lobe=False``: clusters may cross fissures), whose one row is 'whole_lung'.  Also
     'threshold', 'connectivity' and 'components', the per-lobe id volume (int32, -1 outside the clusters).  'd' is the
     exponent of the cumulative cluster-size distribution sampled at powers of two -- NOT Mishima's per-slice 2-D fit
-    over every distinct size.  Device tensors, nothing read back; ``laa_cluster_metrics`` formats it on the host."""
+    over every distinct size.  Device tensors, nothing read back; ``laa_cluster_metrics`` formats it on the host.
+
+    ``shapes`` (off: the result is the above, key for key): the result gains 'shapes', ``shapes_from_rows(bulla_mm, top,
+    origin)`` of ``ops.component_shapes`` on the per-lobe labelling, the class of a cluster read from ``labels`` at its
+    root, plus 'whole_lung' (the same of the whole-lung labelling, every cluster in row 0 of two), 'rows' and
+    'whole_lung_rows' (the raw int64 [m, 18] tables) and 'zone_names'.  No new labelling: two more kernel calls, each
+    of which reads its number of clusters back (the two synchronisations of this function).  ``zones`` (uint8 [D,H,W],
+    ``core_peel``'s 'zones') with ``zone_names`` (``ZONES`` / ``FISSURE_ZONES``, in the order of the zone values 1, 2,
+    3) crosses the clusters with the zones: zone counts per cluster, a home zone, clusters and bullae per row and home
+    zone.  ``origin``: the (z, y, x) offset of the volume in the grid the centroids are reported in."""
     comp, table, _ = ops.laa_components(image, labels, threshold, n_regions, connectivity, by_lobe=True)
-    _, whole, _ = ops.laa_components(image, labels, threshold, 1, connectivity, by_lobe=False)
+    whole_comp, whole, _ = ops.laa_components(image, labels, threshold, 1, connectivity, by_lobe=False)
     out = clusters_from_table(table, spacing)
     out["whole_lung"] = {k: v[1] for k, v in clusters_from_table(whole, spacing).items()}
     out.update(threshold=int(threshold), connectivity=int(connectivity), components=comp)
+    if shapes:
+        if (zones is None) != (zone_names is None):
+            raise ValueError("laa_clusters: zones and zone_names come together")
+        names = () if zone_names is None else tuple(zone_names)
+        if zones is not None and len(names) not in (2, 3):
+            raise ValueError(f"laa_clusters: zone_names must name 2 or 3 zones, got {names}")
+        kw = dict(bulla_mm=bulla_mm, top=top, origin=origin, n_zones=len(names))
+        rows, _ = ops.component_shapes(comp, labels, zones)
+        whole_rows, _ = ops.component_shapes(whole_comp, None, zones)
+        sh = shapes_from_rows(rows, spacing, n_regions, **kw)
+        sh.update(whole_lung=shapes_from_rows(whole_rows, spacing, 1, **kw), rows=rows, whole_lung_rows=whole_rows,
+                  zone_names=names)
+        out["shapes"] = sh
+    return out
+
+
+def _shape_metrics(t: int, sh: dict, names=None) -> dict:
+    """the entries ``laa_cluster_metrics`` adds for a result with 'shapes'"""
+    lung = sh["whole_lung"]
+    cols = [(f"laa{t}_{stem}", _lst(sh[field]), _lst(lung[field])[0], spec, cast) for stem, field, spec, cast in
+            (("bullae", "bullae", "{:d}", int), ("bulla_ml", "bulla_ml", "{:.3f}", float),
+             ("bulla_laa_share", "bulla_laa_share", "{:.3f}", float))]
+    out = _column_metrics("laa_cluster_metrics", cols, names)
+    for i, zone in enumerate(sh["zone_names"]):
+        for stem, field in (("clusters", "zone_clusters"), ("bullae", "zone_bullae")):
+            per_row = _lst(sh[field])
+            out[f"laa{t}_{stem}_per_region_{zone}"] = {_region_key(names, label): "{:d}".format(int(per_row[label][i]))
+                                                       for label in range(1, len(per_row))}
+            out[f"laa{t}_{stem}_per_lung_{zone}"] = "{:d}".format(int(_lst(lung[field])[0][i]))
+    f3 = lambda v: _fmt(float(v), "{:.3f}")
+    region, home = _lst(sh["region"]), _lst(sh["home_zone"])
+    fields = {k: _lst(sh[k]) for k in ("volume_ml", "diameter_mm", "extent_mm", "centroid", "surface_mm2", "sphericity")}
+    largest = []
+    for i in _lst(sh["largest"]):
+        zone = int(home[i])
+        largest.append({"region": _region_key(names, int(region[i])) if int(region[i]) > 0 else None,
+                        "volume_ml": f3(fields["volume_ml"][i]), "diameter_mm": f3(fields["diameter_mm"][i]),
+                        "extent_mm": [f3(v) for v in fields["extent_mm"][i]],
+                        "centroid": [_fmt(float(v), "{:.1f}") for v in fields["centroid"][i]],
+                        "surface_mm2": f3(fields["surface_mm2"][i]), "sphericity": f3(fields["sphericity"][i]),
+                        "zone": sh["zone_names"][zone - 1] if 1 <= zone <= len(sh["zone_names"]) else None})
+    out[f"laa{t}_largest_clusters"] = largest
+    out["bulla_mm"] = "{:.3f}".format(float(sh["bulla_mm"]))
+    out["bulla_min_voxels"] = "{:d}".format(int(sh["bulla_min_voxels"]))
     return out
 
 
@@ -378,7 +519,15 @@ def laa_cluster_metrics(result: dict, names=None) -> dict:
     a mapping or sequence, else the label as a string), for t = |threshold|: 'laa{t}_clusters_per_region' ("{:d}"),
     'laa{t}_largest_cluster_ml_per_region' and 'laa{t}_cluster_d_per_region' ("{:.3f}", None -- json null -- for NaN),
     their whole-lung twins ending '_per_lung' (one value each) and 'laa_cluster_connectivity' ("{:d}").  Row 0 is not
-    reported as a region.  Pure host code."""
+    reported as a region.  Pure host code.
+
+    A result of ``laa_clusters(shapes=True)`` adds 'laa{t}_bullae_per_region' ("{:d}"), 'laa{t}_bulla_ml_per_region' and
+    'laa{t}_bulla_laa_share_per_region' ("{:.3f}", None for NaN) with their '_per_lung' twins; with zones, for each zone
+    Z 'laa{t}_clusters_per_region_Z' and 'laa{t}_bullae_per_region_Z' ("{:d}", by home zone) with '_per_lung' twins;
+    'laa{t}_largest_clusters', the ``top`` clusters of the per-lobe labelling, largest first, each a dict of 'region'
+    (its key through ``names``, None for row 0), 'volume_ml', 'diameter_mm', 'extent_mm' [z, y, x], 'surface_mm2',
+    'sphericity' ("{:.3f}"), 'centroid' [z, y, x] in voxels of the grid of ``origin`` ("{:.1f}") and 'zone' (the home
+    zone's name or None); 'bulla_mm' ("{:.3f}") and 'bulla_min_voxels' ("{:d}")."""
     t = abs(int(result["threshold"]))
     lung = result["whole_lung"]
     cols = [(f"laa{t}_{stem}", _lst(result[field]), _lst(lung[field]), spec, cast) for stem, field, spec, cast in
@@ -386,6 +535,8 @@ def laa_cluster_metrics(result: dict, names=None) -> dict:
              ("cluster_d", "d", "{:.3f}", float))]
     out = _column_metrics("laa_cluster_metrics", cols, names, unsigned_zero=True)   # a slope of +-1e-17 reads 0.000
     out["laa_cluster_connectivity"] = "{:d}".format(int(result["connectivity"]))
+    if "shapes" in result:
+        out.update(_shape_metrics(t, result["shapes"], names))
     return out
 
 
@@ -508,6 +659,10 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     ``clusters`` (independent of the three): the entry also carries ``laa_cluster_metrics`` of ``laa_clusters`` on the
     case's 'image' and 'lobe_labels' before the resize (``cluster_kw``: n_regions, threshold, connectivity), keyed
     through ``region_names``, and a line in error_messages when LAA voxels carry a label above n_regions.
+    ``cluster_kw={'shapes': True, 'bulla_mm': ..., 'top': ...}`` adds the cluster shapes of ``laa_clusters(shapes=True)``
+    to the section (bullae per lobe, the largest clusters; the centroids in voxels of the scan's grid: ``origin`` is the
+    crop's offset); only together with ``core_peel`` the clusters are crossed with that section's zones, which is then
+    issued first.  With shapes off the launch order and the entry are what they are without the key.
     'full_cle' / 'full_pse' are the same bit for bit under every combination.
 
     ``scan_filter`` (None, or a window size of ``ops.median_filter3d``: (3, 3, 3) or (1, 3, 3), ...):
@@ -550,9 +705,21 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=any(on.values()), **prepare_kw)
     filtered = scan_filter is not None and any(on[name] for name in named)
     smooth = filtered_image(case["image"], scan_filter) if filtered else None
-    results = {name: _SECTIONS[name].run(smooth if filtered and name in named else case["image"], case["lobe_labels"],
-                                         spacing, **kw[name])
-               for name in _LAUNCH_ORDER if on[name]}
+    order = _LAUNCH_ORDER
+    shapes = on["clusters"] and bool(kw["clusters"].get("shapes"))
+    if shapes:
+        kw["clusters"]["origin"] = tuple(int(v) for v in case["crop_slice"][:, 0])
+        if core_peel:                               # the clusters are crossed with the section's own zones: it runs first
+            order = ("core_peel",) + tuple(name for name in _LAUNCH_ORDER if name != "core_peel")
+    results = {}
+    for name in order:
+        if not on[name]:
+            continue
+        if name == "clusters" and shapes and core_peel:
+            kw[name].update(zones=results["core_peel"]["zones"],
+                            zone_names=results["core_peel"].get("zone_names", ZONES))
+        results[name] = _SECTIONS[name].run(smooth if filtered and name in named else case["image"], case["lobe_labels"],
+                                            spacing, **kw[name])
     cp = results.get("core_peel")
     # core / peel rides the network side on the regions' tail: its zone labels are the batch's labels, with 2n regions
     # (3n with the fissural rind)

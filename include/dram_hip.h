@@ -798,6 +798,45 @@ int dram_label_components(const void* key_or_labels, int lab_elem, long long str
                           int32_t* components, int32_t* cluster_voxels, int64_t* table, void* work, int D, int H, int W,
                           dram_stream_t stream);
 
+/* Per-component table of a labelled volume: one row per connected component, behind the cluster shapes of the predict
+ * report (csrc/ccl_shapes.hip; definitions: INTEGRATION.md B8).
+ *   components [D,H,W] int32, contiguous, only read: what dram_label_components writes, the linear index of the
+ *     component's smallest voxel, -1 on background.  A voxel v with c = components[v] counts in component c only when
+ *     0 <= c < D*H*W and components[c] == c; any other voxel is background, so no int32 content indexes out of bounds.
+ *   A root is a voxel with components[v] == v; roots are ranked in ascending linear index.
+ *   dram_component_rank: work (dram_component_shapes_workspace(D, H, W) bytes, 256-byte aligned, owned by the caller,
+ *     needs no clearing) receives the rank of every root at the root's slot of an int32 volume -- no other slot is ever
+ *     read -- and count[0] the number of components.  Three launches: root count per workgroup, one ordered scan of
+ *     the workgroup counts by a single workgroup, rank assignment.
+ *   dram_component_shapes: after dram_component_rank on the same components and work.
+ *     labels (optional, NULL) [D,H,W] of lab_elem 1 (uint8) or 2 (int16) bytes per element, read in place through
+ *       stride_z / stride_y (in elements, >= 0; x stride 1) like dram_lobe_hist's labels;
+ *     zones (optional, NULL) [D,H,W] uint8, contiguous: the zones output of dram_lung_zones / dram_lobe_zones;
+ *     rows [capacity][18] int64, row r the component of rank r:
+ *       0 root (the component's id in components), 1 class (labels at the root, raw value, sign-extended for int16; 0
+ *       without labels), 2 voxels, 3..8 z0, z1, y0, y1, x0, x1 (bounding box, half-open like dram_lung_bbox),
+ *       9..11 sum of z, of y, of x over the voxels, 12..14 exposed faces normal to z, to y, to x (a voxel face whose
+ *       neighbour along the axis lies outside the volume or holds another value in components; two components that
+ *       touch each count the shared face), 15..17 voxels with zones == 1, == 2, == 3 (any other zone value counts
+ *       nowhere; 0 without zones);
+ *     count [2] int64: count[0] the number of components, count[1] = min(count[0], capacity) the rows filled; rows
+ *       count[1]..capacity are zeros; a component of rank >= capacity is dropped.  Every output element is written.
+ *     Two launches (row init, accumulate).  One wave per x-row in chunks of 64 voxels: everything that shares a row is
+ *     reduced in the wave first, the last lane of each x-run segment of equal value issues the segment's atomics, and a
+ *     workgroup adds the segments of its large components in LDS before it touches their rows (never one atomic per
+ *     voxel; a single giant component does not serialise the chip on one row).
+ * Integer atomics only (64-bit add, min, max): independent of arrival order, bit-identical from call to call.  No
+ * waiting between workgroups, no ticket word, never synchronises, capturable.  With D*H*W < 2^31 every coordinate sum
+ * is below 2^31 * 2^31 = 2^62: no column can overflow int64.
+ * Null components / work / count, null rows with capacity > 0, capacity < 0, a size < 1, a negative stride, lab_elem
+ * not 1 / 2 with labels: DRAM_ERR_BAD_ARG.  D*H*W >= 2^31: DRAM_ERR_UNSUPPORTED (the workspace function returns 0). */
+long long dram_component_shapes_workspace(int D, int H, int W);
+int dram_component_rank(const int32_t* components, void* work, int64_t* count, int D, int H, int W,
+                        dram_stream_t stream);
+int dram_component_shapes(const int32_t* components, const void* labels, int lab_elem, long long stride_z,
+                          long long stride_y, const uint8_t* zones, const void* work, int64_t* rows, long long capacity,
+                          int64_t* count, int D, int H, int W, dram_stream_t stream);
+
 /* 3-D median filter of an int16 volume (csrc/median.hip; definitions: INTEGRATION.md B9): out[z,y,x] = the median of
  * the (2rz+1)(2ry+1)(2rx+1) values of `in` in the window centred on the voxel, each radius 0 or 1 (3, 9 or 27 samples;
  * (1,1,1) is the 3x3x3 filter, (0,1,1) the in-plane 3x3 one), indices clamped to the volume (edges replicated:
