@@ -10,6 +10,7 @@
 // operands with the ds_read_b128 k-permutation trick of conv_igemm.hip, TN form reads [t][c] rows
 // with ds_read_b32 (lanes = consecutive channels).  Opt-in bf16 matrix-core forms of both (DRAM_MATH,
 // split-bf16 operand images, see split_pack in conv_wino.hip / wino_gemm_nn_bf16_kernel / wino_gemm_tn_bf16_kernel).
+// The fp32 TN GEMM has a streaming form (64 x 128, HBM-bound) and a persistent form (short K) beside its one-tile kernels.
 // Written once and shared: the NN tile decode and operand DMA with its swizzle (one-tile, persistent and bf16 kernels),
 // the lane roles and the fp32 k-group loop (one-tile and persistent kernels), the TN tile / split decode (generic and
 // bf16 kernels).  The LDS-turn epilogue is still written twice, in the one-tile and in the persistent kernel: see the
@@ -682,9 +683,9 @@ struct TnTile {
     return ((long)(tt >> 8) * npts + xi) * 256 + (tt & 255);
   }
 };
-__device__ __forceinline__ TnTile tn_tile(const int bid, const int nblk, const int m_tiles, const int n_tiles,
-                                          const int nsplit, const int kper, const int Tpad) {
-  int L = xcd_remap(bid, nblk);
+// (item L of a launch: n tiles fastest, then m tiles, splits, points)
+__device__ __forceinline__ TnTile tn_item(int L, const int m_tiles, const int n_tiles, const int nsplit, const int kper,
+                                          const int Tpad) {
   TnTile t;
   t.nt = L % n_tiles; L /= n_tiles;
   t.mt = L % m_tiles; L /= m_tiles;
@@ -693,6 +694,10 @@ __device__ __forceinline__ TnTile tn_tile(const int bid, const int nblk, const i
   t.t0 = t.split * kper;
   t.t1 = (t.t0 + kper < Tpad) ? t.t0 + kper : Tpad;
   return t;
+}
+__device__ __forceinline__ TnTile tn_tile(const int bid, const int nblk, const int m_tiles, const int n_tiles,
+                                          const int nsplit, const int kper, const int Tpad) {
+  return tn_item(xcd_remap(bid, nblk), m_tiles, n_tiles, nsplit, kper, Tpad);
 }
 template <int WMW, int MI, int NJ>
 __global__ __launch_bounds__(512) void wino_gemm_tn_kernel(const float* __restrict__ Ah, const float* __restrict__ Bh,
@@ -846,6 +851,252 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_tn64_kernel(const float* __r
     for (int e = 0; e < 16; ++e) {
       const int row = wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
       sb[(long)row * N + wn * 32 + li] = acc[e] + ex[e * 64 + lane];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Persistent form of wino_gemm_tn_kernel for the short-K launches (kper / 32 = 4 k steps: the 128- and 256-channel
+// layers at 16 x 32 x 32, where the one-tile kernel's cold first stage and its store epilogue are as long as its main
+// loop; measured on config 1's shapes, one-tile -> persistent: 256 -> 256 167 -> 155 us, 128 -> 256 90 -> 83, 128 -> 128
+// 45.8 -> 42.7).  A workgroup walks a contiguous run of per_wg items (tn_item order, the runs dealt out XCD by XCD); the FIRST
+// stage of its next item is issued under the last k step of the current one, so it is in flight during that step and
+// the accumulator stores.  Needs an even number of k steps, the same for every item (host-checked), and the two
+// stages as separate LDS objects (the wait-count pass tells DMA targets apart by object only).  Every item is computed
+// exactly as wino_gemm_tn_kernel computes it: same rows per MFMA, same order, same bits (tested).
+template <int WMW, int MI, int NJ>
+__global__ __launch_bounds__(512) void wino_gemm_tn_pers_kernel(const float* __restrict__ Ah, const float* __restrict__ Bh,
+                                                                float* __restrict__ slab, const int Tpad, const int M,
+                                                                const int N, const int m_tiles, const int n_tiles,
+                                                                const int nsplit, const int kper, const int nblk,
+                                                                const int npts, const int per_wg) {
+  constexpr int WNW = 8 / WMW;
+  constexpr int BM = WMW * 32 * MI, BN = WNW * 32 * NJ;
+  static_assert(BM % 64 == 0 && BM <= 256 && BN % 64 == 0 && BN <= 256, "one DMA piece = 256 floats");
+  constexpr int AQ = BM / 4, ARPP = 64 / AQ, APW = BM / 64;   // 16-B slots per row, rows per piece, pieces per wave
+  constexpr int BQ = BN / 4, BRPP = 64 / BQ, BPW = BN / 64;
+  // (A and B rows of a stage apart as well: in one object the reads of the B rows were guarded by a vmcnt(0) against the
+  // DMA just issued into the OTHER stage, seen in the ISA of the forms with NJ >= 2)
+  __shared__ __attribute__((aligned(1024))) float a0[32 * BM], a1[32 * BM];
+  __shared__ __attribute__((aligned(1024))) float b0[32 * BN], b1[32 * BN];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, lh = lane >> 5;
+  const int wm = wave % WMW, wn = wave / WMW;
+  const int first = xcd_remap(blockIdx.x, gridDim.x) * per_wg;
+  const int last = first + per_wg < nblk ? first + per_wg : nblk;
+  if (first >= last) return;
+  const int niter = kper / 32;                               // even, every split whole (host-checked)
+
+  // a lane's DMA sources of an item (the B column clamped into the row: ragged N)
+  auto a_src = [&](const TnTile& t) __attribute__((always_inline)) {
+    return Ah + (long)(lane / AQ) * M + t.mt * BM + (lane % AQ) * 4;
+  };
+  auto b_src = [&](const TnTile& t) __attribute__((always_inline)) {
+    int bcol = t.nt * BN + (lane % BQ) * 4;
+    if (bcol > N - 4) bcol = N - 4;
+    return Bh + (long)(lane / BQ) * N + bcol;
+  };
+  auto issue = [&](const TnTile& t, const float* Ab, const float* Bb, int it, float* as, float* bs)
+      __attribute__((always_inline)) {
+    const long row = t.row(it, npts);
+    const float* ag = Ab + row * M;
+    const float* bg = Bb + row * N;
+#pragma unroll
+    for (int j = 0; j < APW; ++j) {
+      const int p = APW * wave + j;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ag + (long)(p * ARPP) * M),
+                                       (__attribute__((address_space(3))) void*)(as + p * 256), 16, 0, 0);
+    }
+#pragma unroll
+    for (int jj = 0; jj < BPW; ++jj) {
+      const int p = BPW * wave + jj;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bg + (long)(p * BRPP) * N),
+                                       (__attribute__((address_space(3))) void*)(bs + p * 256), 16, 0, 0);
+    }
+  };
+  f32x16 acc[MI][NJ];
+  // the 32 rows of a landed stage, two per MFMA (lane half lh takes row 2 kk + lh), in increasing order
+  auto kstep = [&](const float* sa, const float* sb) __attribute__((always_inline)) {
+    const float* as = sa + wm * 32 * MI + li;
+    const float* bs = sb + wn * 32 * NJ + li;
+#pragma unroll 4
+    for (int kk = 0; kk < 16; ++kk) {
+      const int kr = 2 * kk + lh;
+      float af[MI], bf[NJ];
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) af[mi] = as[kr * BM + mi * 32];
+#pragma unroll
+      for (int nj = 0; nj < NJ; ++nj) bf[nj] = bs[kr * BN + nj * 32];
+#pragma unroll
+      for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+          acc[mi][nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mi], bf[nj], acc[mi][nj], 0, 0, 0);
+    }
+  };
+
+  int idx = first;
+  TnTile cur = tn_item(idx, m_tiles, n_tiles, nsplit, kper, Tpad);
+  const float* Ab = a_src(cur);
+  const float* Bb = b_src(cur);
+  issue(cur, Ab, Bb, 0, a0, b0);
+  for (;;) {
+    const bool more = idx + 1 < last;                         // uniform
+    TnTile nx = cur;
+    if (more) nx = tn_item(idx + 1, m_tiles, n_tiles, nsplit, kper, Tpad);
+    const float* nAb = a_src(nx);
+    const float* nBb = b_src(nx);
+    zero_acc(acc);
+    for (int it = 0; it < niter; it += 2) {
+      __syncthreads();                 // stage 0 (k step it) has landed; stage 1 is free
+      issue(cur, Ab, Bb, it + 1, a1, b1);
+      kstep(a0, b0);
+      __syncthreads();                 // stage 1 has landed; stage 0 is free
+      if (it + 2 < niter) issue(cur, Ab, Bb, it + 2, a0, b0);
+      else if (more) issue(nx, nAb, nBb, 0, a0, b0);             // the NEXT item's first stage: lands under the stores
+      kstep(a1, b1);
+    }
+    float* sb = slab + (((long)cur.split * npts + cur.xi) * M + cur.mt * BM) * N + cur.nt * BN;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = wm * 32 * MI + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+        float* o = sb + (long)row * N + wn * 32 * NJ + li;
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+          if (cur.nt * BN + wn * 32 * NJ + nj * 32 + li < N) o[nj * 32] = acc[mi][nj][e];
+      }
+    if (!more) break;
+    ++idx;
+    cur = nx;
+    Ab = nAb;
+    Bb = nBb;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Streaming form of wino_gemm_tn_kernel<2, 1, 1> for the HBM-bound 64 x 128 launches of the pipeline (the 128 -> 64
+// decoder convolution on 2 x 64 x 128 x 128 voxels moves 5.4 GB through this GEMM).  The one-tile kernel keeps ONE 24-KB
+// stage per workgroup in flight (its per-step __syncthreads() is a vmcnt(0) wait) and fills the chip in 1.125 rounds of
+// workgroups: 4.3 TB/s.  Here a (point, split) chain streams through a ring of S stages of 16 rows (12 KB), filled by
+// LDS-DMA S - 1 stages ahead, with a counted s_waitcnt vmcnt and one s_barrier per stage; 256 threads, <= 128 VGPRs and
+// 36 KB of LDS, so four workgroups share a CU and the 864 chains of a 216-point launch are resident at once.  Every
+// stage -- its A rows and its B rows apart -- is an LDS object of its own: the wait-count pass tells DMA targets apart by
+// object only (with A and B rows in one object the B reads were guarded by a vmcnt(0), seen in the ISA).
+// Four waves as 2 (M) x 2 (N), wave tile 32 x 64: every result sums the rows of its split in increasing order, two per
+// MFMA, lane half lh taking row 2 kk + lh -- the order of wino_gemm_tn_kernel (stage boundaries are multiples of two
+// rows): bit-identical to it (tested).
+// The same ring in the order of wino_gemm_tn64_kernel (64 x 64, one accumulator per k half) was built and measured
+// too: 664 -> 668 us and 87.4 -> 87.2 us on the two 64 -> 64 shapes of config 1 -- that kernel already moves 5.4 TB/s --
+// so those launches stay where they were.
+template <int S>
+__global__ __launch_bounds__(256, 4) void wino_gemm_tn_stream_kernel(const float* __restrict__ Ah, const float* __restrict__ Bh,
+                                                                     float* __restrict__ slab, const int Tpad,
+                                                                     const int nsplit, const int kper, const int nchains,
+                                                                     const int npts) {
+  constexpr int M = 64, N = 128, R = 16;
+  constexpr int IPW = 3;                           // DMA instructions (1 KB) per wave and stage
+  static_assert(S == 3 || S == 4, "ring depth");
+  __shared__ __attribute__((aligned(1024))) float sa0[R * M], sa1[R * M], sa2[R * M], sa3[S == 4 ? R * M : 64];
+  __shared__ __attribute__((aligned(1024))) float sb0[R * N], sb1[R * N], sb2[R * N], sb3[S == 4 ? R * N : 64];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, lh = lane >> 5;
+  const int wm = wave & 1, wn = wave >> 1;
+  // DMA: wave w moves stage rows 4 w .. 4 w + 3 of both operands (A: one piece of 4 rows x 64; B: two of 2 rows x 128)
+  const int a_lane = (lane >> 4) * M + (lane & 15) * 4;
+  const int b_lane = (lane >> 5) * N + (lane & 31) * 4;
+  auto a_of = [&](int k) __attribute__((always_inline)) -> float* {
+    return k == 0 ? sa0 : (k == 1 ? sa1 : (k == 2 ? sa2 : sa3));
+  };
+  auto b_of = [&](int k) __attribute__((always_inline)) -> float* {
+    return k == 0 ? sb0 : (k == 1 ? sb1 : (k == 2 ? sb2 : sb3));
+  };
+
+  for (int c = blockIdx.x; c < nchains; c += gridDim.x) {
+    const int L = xcd_remap(c, nchains);
+    const int split = L % nsplit, xi = L / nsplit;
+    const int t0 = split * kper;
+    const int t1 = (t0 + kper < Tpad) ? t0 + kper : Tpad;
+    const int n = t1 > t0 ? (t1 - t0) / R : 0;     // stages of the chain
+    auto issue = [&](int s, float* sa, float* sb) __attribute__((always_inline)) {
+      // first of the wave's four rows, in one 256-tile block: [g / 256][xi][g % 256 ..]
+      const int g = t0 + R * s + 4 * wave;
+      const long row = ((long)(g >> 8) * npts + xi) * 256 + (g & 255);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Ah + row * M + a_lane),
+                                       (__attribute__((address_space(3))) void*)(sa + wave * 256), 16, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Bh + (row + 2 * j) * N + b_lane),
+                                         (__attribute__((address_space(3))) void*)(sb + (2 * wave + j) * 256), 16, 0, 0);
+    };
+    // the previous chain's stores have retired (the counted waits start from an empty queue) and every wave is done
+    // with its last stages
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    // S - 1 stages ahead.  In front of them stage 0's rows go into the LAST ring slot as well (12 KB per chain, retired
+    // by the first counted wait, overwritten by the first look-ahead): the wait-count pass then meets a DMA into every
+    // stage object before the main loop -- with one met first INSIDE the loop it guarded the reads behind the loop header
+    // with a vmcnt(0), once per S stages (seen in the ISA)
+    if (n > 0) issue(0, a_of(S - 1), b_of(S - 1));
+#pragma unroll
+    for (int k = 0; k < S - 1; ++k)
+      if (k < n) issue(k, a_of(k), b_of(k));
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[a][e] = 0.f;
+
+    // one stage (k = it % S at compile time).  full: every stage up to it + S - 1 exists, so the wait is the counted
+    // one and the look-ahead issue unconditional
+    auto stage = [&](const int k, const int it, const bool full) __attribute__((always_inline)) {
+      // stage `it` has landed for this wave when at most the S - 2 younger stages are outstanding (loads complete in
+      // order); in the tail nothing younger was issued
+      if (full || it + S - 2 < n) __builtin_amdgcn_s_waitcnt(0x0F70 | (IPW * (S - 2)));
+      else __builtin_amdgcn_s_waitcnt(0x0F70);
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_s_barrier();                  // ... and for every wave; all waves are done with stage it - 1
+      if (full || it + S - 1 < n) issue(it + S - 1, a_of((k + S - 1) % S), b_of((k + S - 1) % S));
+      const float* as = a_of(k) + wm * 32 + li;
+      const float* bs = b_of(k) + wn * 64 + li;
+#pragma unroll
+      for (int kk = 0; kk < R / 2; ++kk) {
+        const int kr = 2 * kk + lh;
+        const float af = as[kr * M], b0 = bs[kr * N], b1 = bs[kr * N + 32];
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af, b0, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af, b1, acc[1], 0, 0, 0);
+      }
+    };
+    // Main loop: whole groups of S stages whose look-ahead issues all exist, without a condition inside -- with the
+    // conditional form alone the wait-count pass follows the path "stage issued, the next one not, loop again" (which
+    // never runs) and guards the first reads behind the loop header with a vmcnt(0), once per S stages.  The tail loop
+    // is that conditional form.
+    int itb = 0;
+    for (; itb + 2 * S - 2 < n; itb += S) {
+#pragma unroll
+      for (int k = 0; k < S; ++k) stage(k, itb + k, true);
+    }
+    for (; itb < n; itb += S) {
+#pragma unroll
+      for (int k = 0; k < S; ++k)
+        if (itb + k < n) stage(k, itb + k, false);   // uniform
+    }
+
+    float* sb = slab + (((long)split * npts + xi) * M) * N;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int row = wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+      float* o = sb + (long)row * N + wn * 64 + li;
+      o[0] = acc[0][e];
+      o[32] = acc[1][e];
     }
   }
 }
@@ -1193,6 +1444,58 @@ int run_tn(const float* Ah, const float* Bh, float* slab, const WinoGeom& g, con
   launch(math == 1   ? wino_gemm_tn_bf16_kernel<WM_, MI_, NJ_, 3>      \
          : math == 2 ? wino_gemm_tn_bf16_kernel<WM_, MI_, NJ_, 1>      \
                      : wino_gemm_tn_kernel<WM_, MI_, NJ_>)
+  // fp32: the streaming and the persistent form, bit-identical to the one-tile kernels below (which stay the reference).
+  // The switch is run_nn's, one for the streaming GEMMs of both sides: DRAM_NN_STREAM=0 under DRAM_TUNING=1 = the one-tile
+  // kernels; 1 = by shape (default); 2 = wherever legal and on 8 workgroups, so that small test cases run ring
+  // wrap-around, short tails and several items per workgroup (read per call, the tests flip it)
+  const char* te = tune_env("DRAM_NN_STREAM");
+  const int tn_stream = te ? atoi(te) : 1;
+  if (math == 0 && tn_stream) {
+    // the 64 x 64 launches of the pipeline stay on wino_gemm_tn64_kernel (another order of sums than any form here)
+    const bool t64 = g.npts > 1 && M == 64 && N == 64 && p.kper % 64 == 0 && g.Tpad % 64 == 0;
+    // HBM-bound 64 x 128 launches of the pipeline: the streaming form, one (point, split) chain per workgroup
+    if (g.npts > 1 && M == 64 && N == 128 && p.bm == 64 && p.bn == 128) {
+      const int nchains = g.npts * p.nsplit;
+      const int grid = tn_stream == 2 && nchains > 8 ? 8 : nchains;
+      hipLaunchKernelGGL((wino_gemm_tn_stream_kernel<3>), dim3(grid), dim3(256), 0, s, Ah, Bh, slab, g.Tpad, p.nsplit, p.kper,
+                         nchains, g.npts);
+      DRAM_LAUNCH_CHECK();
+      return DRAM_OK;
+    }
+    // short K (4 k steps per item: the 128- and 256-channel layers at 16 x 32 x 32; measured with 8 steps, 256 -> 512: 284
+    // -> 281 us, inside the run-to-run spread, so those and the 16-step launches of the 512-channel layers, at 0.88 of
+    // the pipe, keep the one-tile kernel): persistent workgroups over whole items, as run_nn sizes its persistent grid --
+    // at most the resident slots (two workgroups per CU up to 64 KB of stages), every workgroup the same number of items
+    // where that costs no round
+    const int niter = p.kper / 32;
+    const bool whole = niter % 2 == 0 && (long)p.kper * p.nsplit == g.Tpad;
+    if (!t64 && whole && (tn_stream == 2 || (g.npts > 1 && niter <= 4))) {
+      const int slots = 256 * (p.bm + p.bn <= 256 ? 2 : 1);
+      const int rounds = (nblk + slots - 1) / slots;
+      int grid = ((nblk + rounds - 1) / rounds + 7) / 8 * 8;
+      if (grid > slots) grid = slots;
+      if (tn_stream == 2) grid = 8;
+      if (grid > nblk) grid = nblk;
+      const int per_wg = (nblk + grid - 1) / grid;
+      grid = (nblk + per_wg - 1) / per_wg;
+      if (per_wg > 1 || tn_stream == 2) {
+#define WTP(WM_, MI_, NJ_)                                                                                              \
+  hipLaunchKernelGGL((wino_gemm_tn_pers_kernel<WM_, MI_, NJ_>), dim3(grid), dim3(512), 0, s, Ah, Bh, slab, g.Tpad, M, N, \
+                     p.m_tiles, p.n_tiles, p.nsplit, p.kper, nblk, g.npts, per_wg)
+        if (p.bm == 256 && p.bn == 256) WTP(4, 2, 4);
+        else if (p.bm == 256 && p.bn == 128) WTP(4, 2, 2);
+        else if (p.bm == 256 && p.bn == 64) WTP(4, 2, 1);
+        else if (p.bm == 128 && p.bn == 256) WTP(2, 2, 2);
+        else if (p.bm == 128 && p.bn == 128) WTP(2, 2, 1);
+        else if (p.bm == 64 && p.bn == 256) WTP(2, 1, 2);
+        else if (p.bm == 64 && p.bn == 128) WTP(2, 1, 1);
+        else return DRAM_ERR_UNSUPPORTED;
+#undef WTP
+        DRAM_LAUNCH_CHECK();
+        return DRAM_OK;
+      }
+    }
+  }
   // (the 64 x 64 kernel sums in another order than the generic 64 x 128 form: pipeline only, so that a 64 -> 64
   // 1x1x1 weight gradient keeps its bits)
   if (math == 0 && g.npts > 1 && M == 64 && N == 64 && p.kper % 64 == 0 && g.Tpad % 64 == 0)
