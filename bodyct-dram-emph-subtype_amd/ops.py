@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 import math
 import os
 import threading
@@ -1708,6 +1709,126 @@ def median_filter3d(image: Tensor, size=(3, 3, 3), out: Optional[Tensor] = None)
         if out is None:
             out = torch.empty_like(image)
         _chk(_L().dram_median3d(_p(image), _p(out), D, H, W, rz, ry, rx, _stream()), "dram_median3d")
+    return out
+
+
+GAUSS_MAX_RADIUS = 16           # DramGaussTaps holds 17 weights per axis
+
+
+def gaussian_radius(sigma: float, truncate: float = 4.0) -> int:
+    """``int(truncate * sigma + 0.5)``, the radius of the reference's ``generate_gaussian_1d_kernel``
+    (functional.py:46).  ValueError for a negative or non-finite sigma and for ``truncate`` <= 0.  Pure host code."""
+    sigma, truncate = float(sigma), float(truncate)
+    if not math.isfinite(sigma) or sigma < 0:
+        raise ValueError(f"gaussian_taps: sigma must be finite and >= 0, got {sigma!r}")
+    if not math.isfinite(truncate) or truncate <= 0:
+        raise ValueError(f"gaussian_taps: truncate must be finite and > 0, got {truncate!r}")
+    return int(truncate * sigma + 0.5)
+
+
+def gaussian_taps(sigma: float, truncate: float = 4.0) -> Tensor:
+    """The reference's ``generate_gaussian_1d_kernel(sigma, truncate)`` (functional.py:44-51) as a CPU float32 tensor
+    [2 r + 1]: r = ``gaussian_radius``, float32 ``exp(-0.5 / sigma^2 * k^2)`` over k = -r..r divided by its float32 sum.
+    ``sigma == 0`` (and any sigma whose radius is 0) gives the single tap 1.0.  ValueError as ``gaussian_radius``, and
+    for a radius above 16, which is what the kernel's tap table holds.  Pure host code."""
+    r = gaussian_radius(sigma, truncate)
+    if r > GAUSS_MAX_RADIUS:
+        raise ValueError(f"gaussian_taps: sigma {float(sigma)!r} x truncate {float(truncate)!r} gives radius {r}; the "
+                         f"filter holds radius <= {GAUSS_MAX_RADIUS}")
+    if r == 0:
+        return torch.ones(1, dtype=torch.float32)
+    k = torch.arange(-r, r + 1)
+    phi = torch.exp(-0.5 / float(sigma) ** 2 * k ** 2)
+    return phi / phi.sum()
+
+
+@functools.lru_cache(maxsize=256)
+def _gauss_half(sigma: float, truncate: float) -> Tuple[float, ...]:
+    """w[0..r] of ``gaussian_taps``: the half the C struct holds (cached: three axes usually share one sigma)"""
+    w = gaussian_taps(sigma, truncate)
+    return tuple(w[w.numel() // 2:].tolist())
+
+
+def _gauss_box(box, shape):
+    """``box`` -- None or [[z0,z1],[y0,y1],[x0,x1]] (a list or ``prepare_case``'s 'crop_slice' tensor) -- as three
+    (lo, hi) pairs of ints inside ``shape``; ValueError otherwise.  The pairs size the output, so they are needed on the
+    host: 'crop_slice' is a host tensor and costs nothing; a box given as a DEVICE tensor is read back here."""
+    if box is None:
+        return [(0, int(n)) for n in shape]
+    try:
+        pairs = [(int(lo), int(hi)) for lo, hi in (box.tolist() if isinstance(box, Tensor) else box)]
+    except (TypeError, ValueError):
+        pairs = []
+    if len(pairs) != 3 or any(not 0 <= lo < hi <= n for (lo, hi), n in zip(pairs, shape)):
+        raise ValueError(f"gaussian_filter3d: box must be [[z0,z1],[y0,y1],[x0,x1]] with 0 <= lo < hi <= size inside "
+                         f"the image {tuple(shape)}, got {box!r}")
+    return pairs
+
+
+def gaussian_filter3d(image: Tensor, sigma, truncate: float = 4.0, mode: str = "nearest", box=None,
+                      out: Optional[Tensor] = None, out_dtype=None) -> Tensor:
+    """Separable Gaussian filter of a volume (csrc/gauss.hip; definitions: INTEGRATION.md B11): along each axis the
+    taps of ``gaussian_taps(sigma_axis, truncate)``, x then y then z, in fp32.
+
+    image [D,H,W] int16 or float32 (made contiguous if it is not; never written); sigma in VOXELS, a number or
+    (z, y, x); an axis whose radius ``int(truncate * sigma + 0.5)`` is 0 is left untouched; mode: 'nearest' (indices
+    clamped to the volume: ``scipy.ndimage.correlate1d(mode='nearest')``) or 'zero' (zeros outside: the reference's
+    ``conv1d(padding='same')``); box: None, or [[z0,z1],[y0,y1],[x0,x1]] (``prepare_case``'s 'crop_slice' as it is):
+    only that box of the filtered volume is computed, and it equals the crop of the whole result bit for bit (the
+    border rule applies at the volume's faces, not the box's); out_dtype: the image's by default; float32 from either,
+    int16 only from int16 (rint of the float32 result, clamped to the int16 range); out: a contiguous tensor of the
+    box's shape and of out_dtype on the image's device that shares no storage with it (default: a new one).  -> out.
+    Fewer than 2^31 voxels.  Two launches and an fp32 intermediate from the shared workspace; the order of the fp32
+    operations of a voxel depends on the taps alone: bit-identical from call to call; never synchronises (give ``box``
+    as a list or a host tensor: a device tensor would be read back first); every check runs before any launch."""
+    if mode not in ("nearest", "zero"):
+        raise ValueError(f"gaussian_filter3d: mode must be 'nearest' or 'zero', got {mode!r}")
+    try:
+        sig = [float(v) for v in sigma] if hasattr(sigma, "__len__") or hasattr(sigma, "__iter__") else [float(sigma)] * 3
+    except (TypeError, ValueError):
+        sig = []
+    if len(sig) != 3:
+        raise ValueError(f"gaussian_filter3d: sigma must be a number or three of them (z, y, x), got {sigma!r}")
+    taps = _lib.DramGaussTaps()
+    for a, s in enumerate(sig):
+        half = _gauss_half(s, float(truncate))
+        taps.radius[a] = len(half) - 1
+        taps.w[a][:len(half)] = half
+    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
+        raise ValueError("gaussian_filter3d: image must be a non-empty [D,H,W] tensor")
+    if image.dtype not in (torch.int16, torch.float32):
+        raise TypeError(f"gaussian_filter3d: expected an int16 or float32 image, got {image.dtype}")
+    if image.numel() >= 2 ** 31:
+        raise ValueError("gaussian_filter3d: volumes of 2^31 voxels or more are not supported")
+    out_dtype = image.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.int16, torch.float32) or (out_dtype == torch.int16 and image.dtype != torch.int16):
+        raise TypeError(f"gaussian_filter3d: out_dtype must be float32, or int16 for an int16 image; got {out_dtype} "
+                        f"for {image.dtype}")
+    (z0, z1), (y0, y1), (x0, x1) = _gauss_box(box, image.shape)
+    shape = (z1 - z0, y1 - y0, x1 - x0)
+    if out is not None:
+        if not isinstance(out, Tensor) or out.dtype != out_dtype:
+            raise TypeError(f"gaussian_filter3d: out must be a {out_dtype} tensor")
+        if tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"gaussian_filter3d: out must be contiguous and of the box's shape {shape}")
+        if out.device != image.device:
+            raise ValueError("gaussian_filter3d: out must live on the image's device")
+        if out.untyped_storage().data_ptr() == image.untyped_storage().data_ptr():
+            raise ValueError("gaussian_filter3d: out must not share storage with image")
+    image = image.contiguous()
+    D, H, W = (int(v) for v in image.shape)
+    code = {torch.int16: 2, torch.float32: 4}
+    with launch_scope(image.device):
+        _req(image, "gaussian_filter3d: image", image.dtype)
+        if out is None:
+            out = torch.empty(shape, device=image.device, dtype=out_dtype)
+        nbytes = int(_L().dram_gauss3d_workspace(D, z0, shape[0], shape[1], shape[2], int(taps.radius[0])))
+        if nbytes < 0:
+            raise RuntimeError("dram_gauss3d_workspace refused the box")
+        ws = _workspace(nbytes, image.device)
+        _chk(_L().dram_gauss3d(_p(image), code[image.dtype], _p(out), code[out_dtype], D, H, W, z0, y0, x0, *shape,
+                               ctypes.byref(taps), 0 if mode == "nearest" else 1, _p(ws), ws.numel() * 4, _stream()),
+             "dram_gauss3d")
     return out
 
 

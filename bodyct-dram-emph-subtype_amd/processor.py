@@ -549,8 +549,53 @@ def filtered_image(case_image: torch.Tensor, size=(3, 3, 3)) -> torch.Tensor:
     return ops.median_filter3d(case_image, size)
 
 
+def gaussian_sigma_mm(fn: str, scan_filter) -> Optional[float]:
+    """The sigma in millimetres of a ``("gaussian", sigma_mm)`` scan filter; None for anything that does not start with
+    the string 'gaussian' (a median window size).  ValueError unless sigma_mm is one finite number > 0.  Pure host code."""
+    if not isinstance(scan_filter, (tuple, list)) or len(scan_filter) < 1 or scan_filter[0] != "gaussian":
+        return None
+    ok = len(scan_filter) == 2 and isinstance(scan_filter[1], (int, float)) and not isinstance(scan_filter[1], bool)
+    if not ok or not math.isfinite(scan_filter[1]) or not scan_filter[1] > 0:
+        raise ValueError(f"{fn}: a Gaussian scan filter is ('gaussian', sigma_mm) with a finite sigma_mm > 0, got "
+                         f"{scan_filter!r}")
+    return float(scan_filter[1])
+
+
+def gaussian_sigma_voxels(fn: str, spacing: Sequence[float], sigma_mm: float) -> Tuple[float, float, float]:
+    """sigma_mm / spacing per axis (z, y, x), in Python floats.  ValueError, naming the axis and its spacing, when the
+    radius ``int(4 sigma + 0.5)`` of an axis exceeds the 16 the filter holds; an axis whose radius is 0 (slices much
+    thicker than sigma) is left untouched by the filter.  Pure host code."""
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f"{fn}: spacing must be three finite numbers > 0 (z, y, x), got {tuple(spacing)!r}")
+    if not (math.isfinite(sigma_mm) and sigma_mm > 0):
+        raise ValueError(f"{fn}: sigma_mm must be finite and > 0, got {sigma_mm!r}")
+    sig = tuple(float(sigma_mm) / v for v in sp)
+    for axis, s, v in zip("zyx", sig, sp):
+        r = ops.gaussian_radius(s)
+        if r > ops.GAUSS_MAX_RADIUS:
+            raise ValueError(f"{fn}: sigma {sigma_mm} mm on axis {axis} with spacing {v} mm is {s:.2f} voxels, radius "
+                             f"{r}; the filter holds radius <= {ops.GAUSS_MAX_RADIUS}")
+    return sig
+
+
+def gaussian_image(scan: torch.Tensor, crop_slice, spacing: Sequence[float], sigma_mm: float) -> torch.Tensor:
+    """The scan-side input of ``densitometry`` / ``core_peel`` / ``laa_clusters`` behind a Gaussian of ``sigma_mm``
+    millimetres: ``ops.gaussian_filter3d`` of the SCAN itself (converted to int16 as
+    ``prepare_case`` converts it), sigma_mm / spacing voxels per axis, edges replicated, evaluated on the box
+    ``crop_slice`` only -> int16 of the crop's shape.  It is the crop of the filtered scan by construction: neither the
+    fill value outside the dilated lung nor the crop's faces enter it.  Device work only: ``crop_slice`` is
+    ``prepare_case``'s host tensor (or a list); a device tensor would be read back to size the output."""
+    sig = gaussian_sigma_voxels("gaussian_image", spacing, float(sigma_mm))
+    return ops.gaussian_filter3d(scan.to(torch.int16), sig, mode="nearest", box=crop_slice)
+
+
 def filter_name(size) -> str:
-    """'median{z}x{y}x{x}' of a window size: the value of the report's 'scan_filter' key."""
+    """The value of the report's 'scan_filter' key: 'median{z}x{y}x{x}' of a median window size, 'gaussian{:.2f}mm' of
+    ``("gaussian", sigma_mm)``."""
+    sigma_mm = gaussian_sigma_mm("filter_name", size)
+    if sigma_mm is not None:
+        return "gaussian{:.2f}mm".format(sigma_mm)
     return "median{}x{}x{}".format(*ops.median_size("filter_name", size))
 
 
@@ -674,13 +719,23 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     argument.  It is an option for noisy scans, and no value of it is recommended.  ValueError, before any device work,
     for a bad size, a name in ``scan_filter_sections`` that is no scan-side section, and ``scan_filter`` together with
     ``dilate_iterations`` < 1 or ``crop_border`` <= 0: only with a dilation and a padded crop does every window centred
-    on a lung voxel hold the scan's own values, so that the filtered crop equals the crop of the filtered scan there."""
+    on a lung voxel hold the scan's own values, so that the filtered crop equals the crop of the filtered scan there.
+
+    ``scan_filter=("gaussian", sigma_mm)`` puts ``gaussian_image`` in the same place: a Gaussian
+    of sigma_mm millimetres (sigma_mm / spacing voxels per axis, truncated at 4 sigma, edges replicated) of the scan
+    ITSELF, evaluated on the crop, so the median's precondition does not apply; the key reads 'gaussian1.00mm'
+    (two decimals).  ValueError, before any device work, for sigma_mm <= 0 and for an axis whose radius exceeds 16 (the
+    message names the axis and its spacing).  No value of sigma_mm is recommended either."""
     named = tuple(scan_filter_sections)
     for name in named:
         if name not in _SECTIONS or _SECTIONS[name].run is None:
             raise ValueError(f"predict_case: scan_filter_sections: {name!r} is not a scan-side section "
                              f"{tuple(k for k, v in _SECTIONS.items() if v.run is not None)}")
-    if scan_filter is not None:
+    sigma_mm = gaussian_sigma_mm("predict_case: scan_filter", scan_filter)
+    if sigma_mm is not None:
+        gaussian_sigma_voxels("predict_case: scan_filter", spacing, sigma_mm)       # the radius cap, per axis
+        scan_filter = ("gaussian", sigma_mm)
+    elif scan_filter is not None:
         scan_filter = ops.median_size("predict_case: scan_filter", scan_filter)
         if int(prepare_kw.get("dilate_iterations", 2)) < 1 or not prepare_kw.get("crop_border", 5) > 0:
             raise ValueError("predict_case: scan_filter needs dilate_iterations >= 1 and crop_border > 0: without them a "
@@ -704,7 +759,10 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
                              "for another count")
     case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=any(on.values()), **prepare_kw)
     filtered = scan_filter is not None and any(on[name] for name in named)
-    smooth = filtered_image(case["image"], scan_filter) if filtered else None
+    if filtered and sigma_mm is not None:
+        smooth = gaussian_image(scan, case["crop_slice"], spacing, sigma_mm)
+    else:
+        smooth = filtered_image(case["image"], scan_filter) if filtered else None
     order = _LAUNCH_ORDER
     shapes = on["clusters"] and bool(kw["clusters"].get("shapes"))
     if shapes:

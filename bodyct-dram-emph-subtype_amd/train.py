@@ -28,7 +28,7 @@ if not __package__:          # imported top-level (this directory on sys.path): 
 import glob
 import logging
 import os
-from argparse import ArgumentParser
+from argparse import SUPPRESS, ArgumentParser
 from pathlib import Path
 
 import torch
@@ -62,6 +62,13 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--synthetic", default=1, type=int)
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--augment", default=0, type=int, help="1: GPU-side train-time augmentations (models.py:66-74)")
+    # default 0.0, carried by the getattr where it is read: SUPPRESS keeps the attribute out of the namespace unless the
+    # flag is given, because tests/test_archive_host.py::test_parser_defaults_and_archive_requirements compares
+    # vars(parse_args([])) with the full dict of defaults (and the namespace is what a run logs as its hyper-parameters)
+    p.add_argument("--augment_smooth", default=SUPPRESS, type=float,
+                   help="with --augment 1: probability of the list's commented-out GaussianSmooth (models.py:68, "
+                        "sigma 0.3-0.6 voxels) between BoxMaskOut and Flip (default: 0.0 = off, the list as the "
+                        "reference runs it)")
     # Lightning Trainer flag the reference exposes through Trainer.add_argparse_args (train.py:46): "bf16" runs the
     # step under autocast(bfloat16) there, the bf16 storage path here
     p.add_argument("--precision", default="32", type=str, choices=("32", "bf16"))
@@ -233,7 +240,8 @@ def run_training_job(argv=None):
     if world > 1:
         from . import distributed as ddist
         ddist.attach(module.model)                 # DDP + SyncBatchNorm semantics (train.py:100-104)
-    augment = TrainAugment() if getattr(args, "augment", 0) else None        # models.py:66-74 (train mode only)
+    # models.py:66-74 (train mode only)
+    augment = TrainAugment(smooth_p=float(getattr(args, "augment_smooth", 0.0) or 0.0)) if getattr(args, "augment", 0) else None
     if args.synthetic:
         data = SyntheticSubtypeData(args.num_samples, args.batch_size, args.target_size, rank, world, device, args.seed)
         val_data = SyntheticSubtypeData(max(args.batch_size * world, args.num_samples // 4), args.batch_size,

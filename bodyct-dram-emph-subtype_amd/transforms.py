@@ -16,6 +16,7 @@ if not __package__:          # imported top-level (this directory on sys.path): 
     __package__ = _dropin.adopt(__name__)
 
 import ctypes
+import dataclasses
 import math
 import random
 from dataclasses import dataclass, field
@@ -334,10 +335,12 @@ def _frac_box(center, size, shape):
 
 @dataclass
 class AugmentParams:
-    """One draw of the four train-time transforms (None / empty = that transform is not applied)."""
+    """One draw of the train-time transforms (None / empty = that transform is not applied).  ``smooth_sigma`` is no
+    field of the C struct: ``augment_image`` runs GaussianSmooth as a call of its own between the boxes and the flip."""
     noise_sigma: Optional[float] = None                                   # GaussianAddictive
     box_centers: List[Tuple[float, float, float]] = field(default_factory=list)   # BoxMaskOut
     box_sizes: List[Tuple[float, float, float]] = field(default_factory=list)
+    smooth_sigma: Optional[float] = None                                  # GaussianSmooth (voxels, isotropic)
     flip_dims: Tuple[int, ...] = ()                                       # Flip (axes of the [D,H,W] volume)
     crop_center: Optional[Tuple[float, float, float]] = None              # CropAndResize
     crop_size: Optional[Tuple[float, float, float]] = None
@@ -372,7 +375,24 @@ class AugmentParams:
 
 def augment_image(image: torch.Tensor, params: AugmentParams, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """image [D,H,W] float32 device tensor -> augmented copy.  `noise` [D,H,W]: the N(0,1) draw of
-    GaussianAddictive (drawn on the device when omitted)."""
+    GaussianAddictive (drawn on the device when omitted).
+
+    With ``params.smooth_sigma`` set the reference's order (models.py:66-74) takes three calls, each with its own
+    transforms only: the fused kernel with noise + boxes, ``ops.gaussian_filter3d(mode='zero')`` (GaussianSmooth:
+    functional.py:54-64), the fused kernel with flip + crop; a call whose transforms are all off is skipped.  The
+    split is exact: noise and boxes act at the source voxel, flip and crop only move the gather, so without the
+    smoothing the two fused calls compose to the single one that is issued then, as before."""
+    if params.smooth_sigma is not None:
+        head = dataclasses.replace(params, smooth_sigma=None, flip_dims=(), crop_center=None, crop_size=None)
+        tail = dataclasses.replace(params, smooth_sigma=None, noise_sigma=None, box_centers=[], box_sizes=[])
+        image = image.float().contiguous()
+        _req(image, "image")
+        if head.to_struct(image.shape).flags:
+            image = augment_image(image, head, noise)
+        image = ops.gaussian_filter3d(image, float(params.smooth_sigma), mode="zero")
+        if tail.to_struct(image.shape).flags:
+            image = augment_image(image, tail)
+        return image
     image = image.float().contiguous()
     _req(image, "image")
     D, H, W = image.shape
@@ -393,7 +413,8 @@ def augment_image(image: torch.Tensor, params: AugmentParams, noise: Optional[to
 
 
 def augment_mask(mask: torch.Tensor, params: AugmentParams) -> torch.Tensor:
-    """mask [D,H,W] -> Flip + CropAndResize(nearest) with the same parameters (DualTransform semantics)."""
+    """mask [D,H,W] -> Flip + CropAndResize(nearest) with the same parameters (DualTransform semantics; the
+    image-only transforms, ``smooth_sigma`` among them, leave a mask alone)."""
     dtype = mask.dtype
     m = mask.float().contiguous()
     _req(m, "mask")
@@ -411,11 +432,24 @@ class TrainAugment:
     GaussianAddictive(p=.5, sigma (0.03, 0.06)), BoxMaskOut(p=.5, 1-10 boxes, centres (0.2, 0.8), sizes
     (0.01, 0.06)), Flip(p=.5, 1-2 of the 3 axes), CropAndResize(p=.5, centre (0.45, 0.55), size (0.95, 1.0)).
     Parameters are drawn on the host like the reference's get_params (same distributions; the streams of
-    Python's / numpy's global generators are not reproduced)."""
+    Python's / numpy's global generators are not reproduced).
 
-    def __init__(self, p: float = 0.5, rng: Optional[random.Random] = None):
+    ``smooth_p`` > 0 switches on the list's commented-out GaussianSmooth (models.py:68) between BoxMaskOut and Flip:
+    with probability ``smooth_p`` a sigma from ``smooth_sigma`` (voxels; the reference's (0.3, 0.6)).  Its two draws
+    are made only then: at the default 0.0 the random stream is consumed exactly as without the argument, and
+    ``smooth_sigma`` is neither drawn from nor checked (with ``smooth_p`` > 0: ValueError unless 0 <= lo <= hi and the
+    radius of hi is at most 16)."""
+
+    def __init__(self, p: float = 0.5, rng: Optional[random.Random] = None, smooth_p: float = 0.0,
+                 smooth_sigma: Tuple[float, float] = (0.3, 0.6)):
         self.p = p
         self.rng = rng or random.Random()
+        self.smooth_p = float(smooth_p)
+        self.smooth_sigma = tuple(float(v) for v in smooth_sigma)
+        if self.smooth_p > 0:                                          # off: the range is never drawn from, nor checked
+            if len(self.smooth_sigma) != 2 or not 0 <= self.smooth_sigma[0] <= self.smooth_sigma[1]:
+                raise ValueError(f"TrainAugment: smooth_sigma must be a range 0 <= lo <= hi, got {smooth_sigma!r}")
+            ops.gaussian_taps(self.smooth_sigma[1])                    # the radius cap, before any draw
 
     def draw(self) -> AugmentParams:
         r, ap = self.rng, AugmentParams()
@@ -425,6 +459,8 @@ class TrainAugment:
             n = r.randint(1, 10)
             ap.box_centers = [tuple(r.uniform(0.2, 0.8) for _ in range(3)) for _ in range(n)]
             ap.box_sizes = [tuple(r.uniform(0.01, 0.06) for _ in range(3)) for _ in range(n)]
+        if self.smooth_p > 0 and r.random() < self.smooth_p:
+            ap.smooth_sigma = r.uniform(*self.smooth_sigma)
         if r.random() < self.p:
             ap.flip_dims = tuple(r.sample(range(3), r.randint(1, 2)))      # np.random.randint(1, 3) axes
         if r.random() < self.p:

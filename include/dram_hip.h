@@ -847,6 +847,38 @@ int dram_component_shapes(const int32_t* components, const void* labels, int lab
  * D*H*W >= 2^31: DRAM_ERR_UNSUPPORTED. */
 int dram_median3d(const int16_t* in, int16_t* out, int D, int H, int W, int rz, int ry, int rx, dram_stream_t stream);
 
+/* Separable 3-D Gaussian (any symmetric tap) filter (csrc/gauss.hip; definitions: INTEGRATION.md B11):
+ *   f[z,y,x] = sum_k wz[k] sum_j wy[j] sum_i wx[i] * in[z+k, y+j, x+i],  evaluated along x, then y, then z, in fp32.
+ * taps (host pointer, read during the call): per axis a in (z, y, x) order the radius r_a in 0..16 and the symmetric half
+ *   w[a][0..r_a] (w[a][k] weighs the two voxels at distance k); radius 0 leaves the axis untouched (w[a][0] is not read).
+ * in [D,H,W] contiguous, in_type 2 (int16) or 4 (float32), only read.  out: the box [z0,z0+Do) x [y0,y0+Ho) x
+ *   [x0,x0+Wo) of f as a contiguous [Do,Ho,Wo] array (the whole volume: origin 0, extents D, H, W); out_type 4
+ *   (float32, from either source) or 2 (int16, from an int16 source: rintf of the same fp32 value, clamped to
+ *   -32768..32767).  Every output element is written.
+ * border: source indices outside the VOLUME (not the box) are clamped (DRAM_GAUSS_NEAREST: edge replication,
+ *   scipy.ndimage mode='nearest') or read as 0 (DRAM_GAUSS_ZERO: conv1d(padding='same'), scipy mode='constant').
+ * Along one axis the value is ((w[0] c + w[1] (l1 + r1)) + w[2] (l2 + r2)) + ..., each `+ w (l + r)` one fused
+ *   multiply-add: the order of the fp32 operations of an output voxel depends on the taps alone -- not on the tile, the
+ *   box, the output type or the call.  So a box equals the crop of the whole result, the int16 output equals rintf of the
+ *   float32 one, and two calls agree, all bit for bit.
+ * Two launches: the in-plane pass (x then y out of LDS, the border rule applied while staging) writes the planes
+ *   [max(0, z0-rz), min(D, z0+Do+rz)) of the box's rows and columns as fp32 into `work`; the z pass sums 2 rz + 1 of
+ *   them per output.  work: dram_gauss3d_workspace(D, z0, Do, Ho, Wo, rz) bytes, 16-byte aligned; work_bytes its size.
+ *   1-D grids, no atomics, never synchronises, capturable.
+ * Null pointer, a size < 1, a radius outside 0..16, a box that leaves the volume, a type pair other than (2,2), (2,4),
+ *   (4,4), a border other than the two, out == in, work not 16-byte aligned or work_bytes too small: DRAM_ERR_BAD_ARG
+ *   (the workspace function returns -1).  D*H*W >= 2^31: DRAM_ERR_UNSUPPORTED. */
+#define DRAM_GAUSS_NEAREST 0
+#define DRAM_GAUSS_ZERO 1
+typedef struct DramGaussTaps {
+  int32_t radius[3];
+  float w[3][17];
+} DramGaussTaps;
+long long dram_gauss3d_workspace(int D, int z0, int Do, int Ho, int Wo, int rz);
+int dram_gauss3d(const void* in, int in_type, void* out, int out_type, int D, int H, int W, int z0, int y0, int x0,
+                 int Do, int Ho, int Wo, const DramGaussTaps* taps, int border, void* work, long long work_bytes,
+                 dram_stream_t stream);
+
 /* Train-time augmentations (models.py:66-74) with GIVEN parameters, fused into one gather pass:
  * GaussianAddictive (intensity_transforms.py:145-177; noise [D,H,W] supplied by the caller, minmax[2] = volume
  * {min, max} on the device, e.g. folded from dram_minmax partials [nblk][2]), BoxMaskOut (:180-237), Flip
