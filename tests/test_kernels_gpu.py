@@ -4,6 +4,8 @@ Tolerances: fp32 kernels vs fp32 CPU ops, different summation order -> relative 
 1e-5..1e-4 per tensor (stated per test); the end-to-end 1e-3 bar of BASELINE.json is
 checked in test_network_gpu.py.
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -94,7 +96,7 @@ def test_conv3d_fwd_bwd(ops, monkeypatch, case):
     dx3 = ops.conv3d_bwd_data(gyd, wb, g, to_ndhwc(add), None)
     assert rel_l2(to_ncdhw(dx3), gx_ref + add) < 2e-6
 
-    if Cin % 64 == 0:
+    if ops._L().dram_conv3d_bwd_weight_workspace(ctypes.byref(g.desc())):      # every geometry the direct kernels take
         dw = ops.conv3d_bwd_weight(xd, gyd, g)
         assert rel_l2(dw.cpu(), gw_ref) < 5e-6
 
