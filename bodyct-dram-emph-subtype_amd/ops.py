@@ -1832,6 +1832,126 @@ def gaussian_filter3d(image: Tensor, sigma, truncate: float = 4.0, mode: str = "
     return out
 
 
+BILAT_MAX_RADIUS = _lib.DRAM_BILAT_MAX_RADIUS       # DramBilateral holds 6 spatial entries per axis ...
+BILAT_RANGE_LEN = _lib.DRAM_BILAT_RANGE_LEN         # ... and 1024 range entries
+
+
+def bilateral_radius(sigma: float, truncate: float = 2.0) -> int:
+    """``int(truncate * sigma + 0.5)``, the radius of one axis of ``bilateral_filter3d``.  ValueError for a negative or
+    non-finite sigma and for ``truncate`` <= 0.  Pure host code."""
+    sigma, truncate = float(sigma), float(truncate)
+    if not math.isfinite(sigma) or sigma < 0:
+        raise ValueError(f"bilateral_tables: sigma must be finite and >= 0, got {sigma!r}")
+    if not math.isfinite(truncate) or truncate <= 0:
+        raise ValueError(f"bilateral_tables: truncate must be finite and > 0, got {truncate!r}")
+    return int(truncate * sigma + 0.5)
+
+
+@functools.lru_cache(maxsize=64)
+def _bilateral_tables(sig: Tuple[float, float, float], sigma_hu: float, truncate: float):
+    spatial = []
+    for axis, s in zip("zyx", sig):
+        r = bilateral_radius(s, truncate)
+        if r > BILAT_MAX_RADIUS:
+            raise ValueError(f"bilateral_tables: sigma {s!r} x truncate {truncate!r} on axis {axis} gives radius {r}; the "
+                             f"filter holds radius <= {BILAT_MAX_RADIUS}")
+        spatial.append(tuple(int(math.floor(256.0 * math.exp(-(k * k) / (2.0 * s * s)) + 0.5)) for k in range(r + 1))
+                       if r else (256,))
+    if not math.isfinite(sigma_hu) or not sigma_hu > 0:
+        raise ValueError(f"bilateral_tables: sigma_hu must be finite and > 0, got {sigma_hu!r}")
+    two_var = 2.0 * sigma_hu * sigma_hu
+    rng = []
+    while not rng or rng[-1] != 0:
+        d = len(rng)
+        if d > BILAT_RANGE_LEN:                         # the first zero lies beyond the table
+            break
+        rng.append(int(math.floor(256.0 * math.exp(-(d * d) / two_var) + 0.5)) if two_var > 0.0 else (256 if d == 0 else 0))
+    if rng[-1] != 0 or len(rng) > BILAT_RANGE_LEN:
+        raise ValueError(f"bilateral_tables: sigma_hu {sigma_hu!r} needs a range table of more than {BILAT_RANGE_LEN} "
+                         "entries")
+    return spatial[0], spatial[1], spatial[2], tuple(rng)
+
+
+def _sigma3(fn: str, sigma) -> Tuple[float, float, float]:
+    try:
+        sig = [float(v) for v in sigma] if hasattr(sigma, "__len__") or hasattr(sigma, "__iter__") else [float(sigma)] * 3
+    except (TypeError, ValueError):
+        sig = []
+    if len(sig) != 3:
+        raise ValueError(f"{fn}: sigma must be a number or three of them (z, y, x), got {sigma!r}")
+    return tuple(sig)
+
+
+def bilateral_tables(sigma, sigma_hu: float, truncate: float = 2.0):
+    """The integer tables of ``bilateral_filter3d`` -> (T_z, T_y, T_x, R), four lists of ints.
+    sigma in VOXELS, a number or (z, y, x).  Per axis r = ``bilateral_radius`` and ``T[k] = floor(256 exp(-k^2 /
+    (2 sigma^2)) + 0.5)`` for k = 0..r, [256] for r = 0; ``R[d] = floor(256 exp(-d^2 / (2 sigma_hu^2)) + 0.5)`` for
+    d = 0, 1, ... up to and including the first d with R[d] = 0.  ValueError for a radius above 5 (naming the axis), a
+    sigma_hu that is not finite and > 0, and a range table of more than 1024 entries.  Python floats; pure host code."""
+    tz, ty, tx, rng = _bilateral_tables(_sigma3("bilateral_tables", sigma), float(sigma_hu), float(truncate))
+    return list(tz), list(ty), list(tx), list(rng)
+
+
+@functools.lru_cache(maxsize=64)
+def _bilateral_struct(sig: Tuple[float, float, float], sigma_hu: float, truncate: float):
+    """the tables as the C struct (cached; only read by the calls)"""
+    *spatial, rng = _bilateral_tables(sig, sigma_hu, truncate)
+    tab = _lib.DramBilateral()
+    for a, t in enumerate(spatial):
+        tab.radius[a] = len(t) - 1
+        tab.spatial[a][:len(t)] = t
+    tab.range_len = len(rng)
+    tab.range[:len(rng)] = rng
+    return tab
+
+
+def bilateral_filter3d(image: Tensor, sigma, sigma_hu: float, truncate: float = 2.0, within: Optional[Tensor] = None,
+                       out: Optional[Tensor] = None) -> Tensor:
+    """Bilateral filter of a scan in exact integer fixed point (csrc/bilateral.hip; definitions: INTEGRATION.md B12).
+    With (T_z, T_y, T_x, R) = ``bilateral_tables(sigma, sigma_hu, truncate)`` and L = len(R), a tap at (dz, dy, dx)
+    weighs ``S = (T_z[|dz|] T_y[|dy|] T_x[|dx|] + 2^15) >> 16`` in space, and per centre c, over the taps inside the
+    volume (and inside ``within``), ``d = v - v_c``, ``w = S R[min(|d|, L - 1)]``, ``num = sum w d``, ``den = sum w``,
+    ``out_c = v_c + floor((2 num + den) / (2 den))``.
+
+    image [D,H,W] int16 (made contiguous if it is not; never written); sigma in VOXELS, a number or (z, y, x), every
+    radius ``int(truncate * sigma + 0.5)`` <= 5, an axis of radius 0 is left untouched; sigma_hu > 0 in the image's
+    units, its range table at most 1024 long (sigma_hu <= 289); within: None, or a label volume [D,H,W] uint8 / int16 /
+    bool read in place like ``lobe_histogram``'s labels: only voxels with ``within != 0`` are taps, and a voxel with
+    ``within == 0`` keeps its value; out: an int16 contiguous tensor of the image's shape that shares no storage with
+    it (default: a new one).  -> out.  Nothing outside the volume is read: no border rule.  Fewer than 2^31 voxels.
+    One launch, integers only: bit-identical from call to call; never synchronises; every check runs before any launch."""
+    tab = _bilateral_struct(_sigma3("bilateral_filter3d", sigma), float(sigma_hu), float(truncate))
+    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
+        raise ValueError("bilateral_filter3d: image must be a non-empty [D,H,W] tensor")
+    if image.dtype != torch.int16:
+        raise TypeError(f"bilateral_filter3d: expected an int16 image, got {image.dtype}")
+    if image.numel() >= 2 ** 31:
+        raise ValueError("bilateral_filter3d: volumes of 2^31 voxels or more are not supported")
+    if out is not None:
+        if not isinstance(out, Tensor) or out.dtype != torch.int16:
+            raise TypeError("bilateral_filter3d: out must be an int16 tensor")
+        if tuple(out.shape) != tuple(image.shape) or not out.is_contiguous():
+            raise ValueError(f"bilateral_filter3d: out must be contiguous and of the image's shape {tuple(image.shape)}")
+        if out.device != image.device:
+            raise ValueError("bilateral_filter3d: out must live on the image's device")
+        if out.untyped_storage().data_ptr() == image.untyped_storage().data_ptr():
+            raise ValueError("bilateral_filter3d: out must not share storage with image")
+    code, sz, sy = 0, 0, 0
+    if within is not None:
+        within, code, sz, sy = _label_view("bilateral_filter3d", within, "within", tuple(image.shape))
+        if within.device != image.device:
+            raise RuntimeError("bilateral_filter3d: within must live on the image's device")
+    image = image.contiguous()
+    D, H, W = (int(v) for v in image.shape)
+    with launch_scope(image.device):
+        _req(image, "bilateral_filter3d: image", torch.int16)
+        if out is None:
+            out = torch.empty_like(image)
+        _chk(_L().dram_bilateral3d(_p(image), _p(out), _p(within), code, sz, sy, D, H, W, ctypes.byref(tab), _stream()),
+             "dram_bilateral3d")
+    return out
+
+
 # --------------------------------------------------------------------------- heads / losses
 def head_fwd(x: Tensor, w: Tensor, bias: Tensor, lungs: Optional[Tensor], sigmoid: bool):
     """x [B,D,H,W,32] (float32 or bfloat16); w [NO,32]; lungs None or [B,Dl,Hl,Wl] full-res mask.  The dense maps

@@ -590,9 +590,55 @@ def gaussian_image(scan: torch.Tensor, crop_slice, spacing: Sequence[float], sig
     return ops.gaussian_filter3d(scan.to(torch.int16), sig, mode="nearest", box=crop_slice)
 
 
+def bilateral_params(fn: str, scan_filter) -> Optional[Tuple[float, float]]:
+    """(sigma_mm, sigma_hu) of a ``("bilateral", sigma_mm, sigma_hu)`` scan filter; None for anything that does not
+    start with the string 'bilateral'.  ValueError unless both are finite numbers > 0 (no bools).  Pure host code."""
+    if not isinstance(scan_filter, (tuple, list)) or len(scan_filter) < 1 or scan_filter[0] != "bilateral":
+        return None
+    ok = len(scan_filter) == 3 and all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+                                       and v > 0 for v in scan_filter[1:])
+    if not ok:
+        raise ValueError(f"{fn}: a bilateral scan filter is ('bilateral', sigma_mm, sigma_hu) with finite sigma_mm > 0 "
+                         f"and sigma_hu > 0, got {scan_filter!r}")
+    return float(scan_filter[1]), float(scan_filter[2])
+
+
+def bilateral_sigma_voxels(fn: str, spacing: Sequence[float], sigma_mm: float) -> Tuple[float, float, float]:
+    """sigma_mm / spacing per axis (z, y, x), in Python floats, as ``gaussian_sigma_voxels`` forms it.  ValueError,
+    naming the axis and its spacing, when the radius ``int(2 sigma + 0.5)`` of an axis exceeds the 5 the bilateral
+    filter holds; an axis whose radius is 0 is left untouched by the filter.  Pure host code."""
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f"{fn}: spacing must be three finite numbers > 0 (z, y, x), got {tuple(spacing)!r}")
+    if not (math.isfinite(sigma_mm) and sigma_mm > 0):
+        raise ValueError(f"{fn}: sigma_mm must be finite and > 0, got {sigma_mm!r}")
+    sig = tuple(float(sigma_mm) / v for v in sp)
+    for axis, s, v in zip("zyx", sig, sp):
+        r = ops.bilateral_radius(s)
+        if r > ops.BILAT_MAX_RADIUS:
+            raise ValueError(f"{fn}: sigma {sigma_mm} mm on axis {axis} with spacing {v} mm is {s:.2f} voxels, radius "
+                             f"{r}; the filter holds radius <= {ops.BILAT_MAX_RADIUS}")
+    return sig
+
+
+def bilateral_image(case_image: torch.Tensor, lobe_labels: torch.Tensor, spacing: Sequence[float], sigma_mm: float,
+                    sigma_hu: float) -> torch.Tensor:
+    """The scan-side input of ``densitometry`` / ``core_peel`` / ``laa_clusters`` behind the bilateral filter
+    (INTEGRATION.md B12): ``ops.bilateral_filter3d`` of ``prepare_case``'s 'image' (int16 [D,H,W]) with sigma_mm /
+    spacing voxels per axis, truncated at 2 sigma, ``sigma_hu`` in HU and ``within=lobe_labels``, a new tensor.  Taps
+    never leave the lung, so neither the fill value outside the dilated lung nor the crop's faces enter a lung voxel:
+    there the result is the crop of the filtered whole scan (``within`` the whole lobe volume) under any
+    ``dilate_iterations`` / ``crop_border``; a voxel outside the lung keeps the case's value.  Device work only."""
+    sig = bilateral_sigma_voxels("bilateral_image", spacing, float(sigma_mm))
+    return ops.bilateral_filter3d(case_image, sig, float(sigma_hu), within=lobe_labels)
+
+
 def filter_name(size) -> str:
     """The value of the report's 'scan_filter' key: 'median{z}x{y}x{x}' of a median window size, 'gaussian{:.2f}mm' of
-    ``("gaussian", sigma_mm)``."""
+    ``("gaussian", sigma_mm)``, 'bilateral{:.2f}mm{:.1f}hu' of ``("bilateral", sigma_mm, sigma_hu)``."""
+    bilateral = bilateral_params("filter_name", size)
+    if bilateral is not None:
+        return "bilateral{:.2f}mm{:.1f}hu".format(*bilateral)
     sigma_mm = gaussian_sigma_mm("filter_name", size)
     if sigma_mm is not None:
         return "gaussian{:.2f}mm".format(sigma_mm)
@@ -725,14 +771,26 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     of sigma_mm millimetres (sigma_mm / spacing voxels per axis, truncated at 4 sigma, edges replicated) of the scan
     ITSELF, evaluated on the crop, so the median's precondition does not apply; the key reads 'gaussian1.00mm'
     (two decimals).  ValueError, before any device work, for sigma_mm <= 0 and for an axis whose radius exceeds 16 (the
-    message names the axis and its spacing).  No value of sigma_mm is recommended either."""
+    message names the axis and its spacing).  No value of sigma_mm is recommended either.
+
+    ``scan_filter=("bilateral", sigma_mm, sigma_hu)`` puts ``bilateral_image`` there: the exact
+    fixed-point bilateral filter of the case's 'image' (sigma_mm / spacing voxels per axis, truncated at 2 sigma;
+    sigma_hu in HU) whose taps are confined to the lobe labels, so the median's precondition does not apply either
+    (``dilate_iterations=0`` is accepted); the key reads 'bilateral1.00mm60.0hu'.  ValueError, before any device work,
+    unless both are finite numbers > 0, for an axis whose radius exceeds 5 (the message names the axis and its spacing)
+    and for a sigma_hu whose range table exceeds 1024 entries (above 289).  No values are recommended."""
     named = tuple(scan_filter_sections)
     for name in named:
         if name not in _SECTIONS or _SECTIONS[name].run is None:
             raise ValueError(f"predict_case: scan_filter_sections: {name!r} is not a scan-side section "
                              f"{tuple(k for k, v in _SECTIONS.items() if v.run is not None)}")
     sigma_mm = gaussian_sigma_mm("predict_case: scan_filter", scan_filter)
-    if sigma_mm is not None:
+    bilateral = bilateral_params("predict_case: scan_filter", scan_filter)
+    if bilateral is not None:
+        sig = bilateral_sigma_voxels("predict_case: scan_filter", spacing, bilateral[0])    # the radius cap, per axis
+        ops.bilateral_tables(sig, bilateral[1])                                             # the range table's cap
+        scan_filter = ("bilateral",) + bilateral
+    elif sigma_mm is not None:
         gaussian_sigma_voxels("predict_case: scan_filter", spacing, sigma_mm)       # the radius cap, per axis
         scan_filter = ("gaussian", sigma_mm)
     elif scan_filter is not None:
@@ -759,7 +817,9 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
                              "for another count")
     case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=any(on.values()), **prepare_kw)
     filtered = scan_filter is not None and any(on[name] for name in named)
-    if filtered and sigma_mm is not None:
+    if filtered and bilateral is not None:
+        smooth = bilateral_image(case["image"], case["lobe_labels"], spacing, *bilateral)
+    elif filtered and sigma_mm is not None:
         smooth = gaussian_image(scan, case["crop_slice"], spacing, sigma_mm)
     else:
         smooth = filtered_image(case["image"], scan_filter) if filtered else None

@@ -879,6 +879,32 @@ int dram_gauss3d(const void* in, int in_type, void* out, int out_type, int D, in
                  int Do, int Ho, int Wo, const DramGaussTaps* taps, int border, void* work, long long work_bytes,
                  dram_stream_t stream);
 
+/* Bilateral filter of an int16 volume in exact integer fixed point, optionally confined to a label volume
+ * (csrc/bilateral.hip; definitions: INTEGRATION.md B12).  tab (host pointer, read during the call, handed to the kernel
+ * by value): per axis a in (z, y, x) order the radius r_a in 0..5 and the spatial table spatial[a][0..r_a] (values
+ * 0..256, spatial[a][0] = 256); range_len = L in 2..1024 and range[0..L-1] (values 0..256, range[0] = 256, range[L-1] = 0).
+ *   S(dz,dy,dx) = (spatial[0][|dz|] * spatial[1][|dy|] * spatial[2][|dx|] + 2^15) >> 16; a tap with S = 0 does not exist.
+ *   Per centre c, over the taps i inside the volume and (with `within`) at voxels where within != 0:
+ *     d_i = v_i - v_c,  w_i = S_i * range[min(|d_i|, L-1)],  num = sum w_i d_i (64-bit),  den = sum w_i;
+ *     out_c = v_c + floor((2 num + den) / (2 den));  with `within` and within_c == 0: out_c = v_c.
+ * in, out [D,H,W] contiguous, any 2-byte alignment, out != in; `in` is only read.  within: NULL, or [D,H,W] of
+ * within_type 1 (uint8) or 2 (int16), read in place through within_sz / within_sy (in elements, >= 0; x stride 1).
+ * One launch, every output element written; integers only: exact, no atomics, no workspace, never synchronises,
+ * capturable; bit-identical from call to call.
+ * Null in / out / tab, out == in, a size < 1, a radius outside 0..5, a table entry outside 0..256, spatial[a][0] != 256,
+ * L outside 2..1024, range[0] != 256, range[L-1] != 0, within with a type other than 1 / 2 or a negative stride: DRAM_ERR_BAD_ARG.
+ * D*H*W >= 2^31: DRAM_ERR_UNSUPPORTED. */
+#define DRAM_BILAT_MAX_RADIUS 5
+#define DRAM_BILAT_RANGE_LEN 1024
+typedef struct DramBilateral {
+  int32_t radius[3];
+  int32_t spatial[3][6];
+  int32_t range_len;
+  int32_t range[1024];
+} DramBilateral;
+int dram_bilateral3d(const int16_t* in, int16_t* out, const void* within, int within_type, long long within_sz,
+                     long long within_sy, int D, int H, int W, const DramBilateral* tab, dram_stream_t stream);
+
 /* Train-time augmentations (models.py:66-74) with GIVEN parameters, fused into one gather pass:
  * GaussianAddictive (intensity_transforms.py:145-177; noise [D,H,W] supplied by the caller, minmax[2] = volume
  * {min, max} on the device, e.g. folded from dram_minmax partials [nblk][2]), BoxMaskOut (:180-237), Flip
