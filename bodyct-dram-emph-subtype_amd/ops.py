@@ -1408,7 +1408,118 @@ def lobe_histogram(image: Tensor, labels: Tensor, n_regions: int = 5, hu_lo: int
     return hist, sums
 
 
-EDT_FULL_UM = 1 << 26           # max_um from here on is the full transform (no distance in a supported volume reaches it)
+LOCAL_MAX_RADIUS = _lib.DRAM_BOXFRAC_MAX_RADIUS      # (2 * 16 + 1)^3 < 2^16: both counts of a box share one 32-bit word
+
+
+def local_window(spacing, local_mm) -> Tuple[int, int, int]:
+    """The radii (rz, ry, rx) in voxels of the box of ``local_fraction3d`` whose sides are ``local_mm`` millimetres, in
+    whole micrometres like ``lung_zones_units``: ``r_a = round(local_mm * 1000) // (2 * round(spacing_a * 1000))``.  The
+    box has 2 r + 1 voxels per axis: at most ``local_mm`` plus one voxel, and an axis whose voxels are larger than
+    ``local_mm / 2`` is one voxel thick.  ValueError for a spacing or ``local_mm`` that is not positive and finite (or
+    rounds to 0 um), for an axis whose radius exceeds 16 (the message names the axis and its spacing) and when all
+    three radii are 0: the window would hold one voxel.  Pure host code."""
+    try:
+        sp = [float(v) for v in spacing]
+    except (TypeError, ValueError):
+        sp = []
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f"local_window: spacing must be three finite numbers > 0 (z, y, x), got {spacing!r}")
+    if isinstance(local_mm, bool) or not isinstance(local_mm, (int, float)) or not math.isfinite(local_mm) or not local_mm > 0:
+        raise ValueError(f"local_window: local_mm must be one finite number > 0, got {local_mm!r}")
+    s_um, l_um = [int(round(v * 1000.0)) for v in sp], int(round(float(local_mm) * 1000.0))
+    if min(s_um) < 1 or l_um < 1:
+        raise ValueError(f"local_window: spacing {tuple(sp)} mm and local_mm {local_mm} must round to at least 1 um")
+    radius = tuple(l_um // (2 * s) for s in s_um)
+    for axis, r, v in zip("zyx", radius, sp):
+        if r > LOCAL_MAX_RADIUS:
+            raise ValueError(f"local_window: local_mm {local_mm} on axis {axis} with spacing {v} mm is radius {r}; the "
+                             f"box count holds radius <= {LOCAL_MAX_RADIUS}")
+    if max(radius) == 0:
+        raise ValueError(f"local_window: local_mm {local_mm} is below two voxels on every axis of spacing {tuple(sp)} "
+                         "mm: the window would hold one voxel")
+    return radius
+
+
+def _local_radius(fn: str, radius) -> Tuple[int, int, int]:
+    try:
+        r = tuple(-1 if isinstance(v, bool) else v.__index__() for v in radius)      # ints and numpy's, no floats
+    except (TypeError, AttributeError):
+        r = ()
+    if len(r) != 3 or min(r) < 0:
+        raise ValueError(f"{fn}: radius must be three integers >= 0 (rz, ry, rx), got {radius!r}")
+    if max(r) > LOCAL_MAX_RADIUS:
+        raise ValueError(f"{fn}: radius {r} exceeds the {LOCAL_MAX_RADIUS} the box count holds")
+    return r
+
+
+def local_fraction3d(image: Tensor, labels: Tensor, threshold: int = -950, radius=(1, 1, 1), out: Optional[Tensor] = None,
+                     out_u8: Optional[Tensor] = None, want_counts: bool = False):
+    """Local low-attenuation fraction (csrc/boxfrac.hip; definitions: INTEGRATION.md B13): at every lung voxel the share,
+    in per mille, of the lung voxels in the box [z +- rz] x [y +- ry] x [x +- rx] around it (clipped to the volume) whose
+    HU value is below ``threshold`` (strict, as in ``densitometry``).  Lung voxels of ANY label count, not only those of
+    the voxel's own lobe.
+
+    image [D,H,W] int16 HU, contiguous; labels [D,H,W] uint8 / int16 / bool, read in place like ``lobe_histogram``'s
+    (lung = label > 0); threshold an integer in -32768..32768; radius (rz, ry, rx), integers in 0..16
+    (``local_window`` gives them for a window in millimetres).  -> map [D,H,W] int16: q = (2000 num + den) // (2 den),
+    0..1000, rounded half up, where the label is positive and -1 elsewhere; with ``want_counts`` (map, counts), counts
+    [D,H,W] int32 = num << 16 | den at EVERY voxel (den: lung voxels in the box, num: those below the threshold; read
+    num as ``(c >> 16) & 0xffff``: it passes 32 767 in the largest boxes).
+    out: an int16 contiguous tensor of the image's shape (default: a new one).  out_u8: a uint8 [D,H,W] VIEW (x stride 1,
+    rows and planes disjoint), e.g. the crop's window of a zero-filled volume of the scan's size: it receives
+    (q * 255) // 1000, 0 where q = -1, and nothing outside the view is written.  Neither may share storage with an
+    input.  Fewer than 2^31 voxels.  Two launches and a 32-bit intermediate from the shared workspace; integers only:
+    bit-identical from call to call; the inputs are only read; never synchronises; every check runs before any launch."""
+    fn = "local_fraction3d"
+    rz, ry, rx = _local_radius(fn, radius)
+    if isinstance(threshold, bool) or int(threshold) != threshold or not -32768 <= int(threshold) <= 32768:
+        raise ValueError(f"{fn}: threshold must be an integer in -32768..32768, got {threshold!r}")
+    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
+        raise ValueError(f"{fn}: image must be a non-empty [D,H,W] tensor")
+    if image.dtype != torch.int16:
+        raise TypeError(f"{fn}: expected an int16 image, got {image.dtype}")
+    D, H, W = (int(v) for v in image.shape)
+    for name, t, dtype in (("out", out, torch.int16), ("out_u8", out_u8, torch.uint8)):
+        if t is None:
+            continue
+        if not isinstance(t, Tensor) or t.dtype != dtype:
+            raise TypeError(f"{fn}: {name} must be a {dtype} tensor")
+        if tuple(t.shape) != (D, H, W):
+            raise ValueError(f"{fn}: {name} must have the image's shape {(D, H, W)}, got {tuple(t.shape)}")
+        if t.device != image.device:
+            raise ValueError(f"{fn}: {name} must live on the image's device")
+        others = [image] + ([labels] if isinstance(labels, Tensor) else []) + ([out] if t is out_u8 and out is not None else [])
+        if any(t.untyped_storage().data_ptr() == o.untyped_storage().data_ptr() for o in others):
+            raise ValueError(f"{fn}: {name} must not share storage with image, labels or the other output")
+    if out is not None and not out.is_contiguous():
+        raise ValueError(f"{fn}: out must be contiguous")
+    uz = uy = 0
+    if out_u8 is not None:
+        uz, uy, ux = (int(v) for v in out_u8.stride())
+        if (W > 1 and ux != 1) or uz < 0 or uy < 0 or (H > 1 and uy < W) or (D > 1 and uz < (H - 1) * uy + W):
+            raise ValueError(f"{fn}: out_u8 must be a view with x stride 1 whose rows and planes are disjoint, got strides "
+                             f"{tuple(out_u8.stride())}")
+    if not image.is_contiguous():
+        raise ValueError(f"{fn}: image must be contiguous")
+    labels, code, sz, sy = _label_view(fn, labels, "labels", image.shape)
+    if labels.device != image.device:
+        raise ValueError(f"{fn}: labels must live on the image's device")
+    dev = image.device
+    with launch_scope(dev):
+        _req(image, f"{fn}: image", torch.int16)
+        if out is None:
+            out = torch.empty((D, H, W), device=dev, dtype=torch.int16)
+        counts = torch.empty((D, H, W), device=dev, dtype=torch.int32) if want_counts else None
+        nbytes = int(_L().dram_boxfrac3d_workspace(D, H, W))
+        if nbytes < 0:
+            raise RuntimeError("dram_boxfrac3d_workspace refused the volume")
+        ws = _workspace(nbytes, dev)
+        _chk(_L().dram_boxfrac3d(_p(image), _p(labels), code, sz, sy, int(threshold), rz, ry, rx, _p(counts), _p(out),
+                                 _p(out_u8), uz, uy, _p(ws), ws.numel() * 4, D, H, W, _stream()), "dram_boxfrac3d")
+    return (out, counts) if want_counts else out
+
+
+EDT_FULL_UM = 1 << 26          # max_um from here on is the full transform (no distance in a supported volume reaches it)
 
 
 def lung_zones_units(spacing, peel_mm, max_mm=None, fn: str = "lung_zones"):

@@ -118,7 +118,8 @@ def region_metrics(table_row, names=None) -> dict:
 
 
 # --------------------------------------------------------------------------- per-lobe CT densitometry
-_DENSITO_KEY = re.compile(r"(laa\d+_fraction|perc\d+_hu|mean_lung_density|volume_ml)_per_(region|lung)")
+_DENSITO_KEY = re.compile(r"(laa\d+_fraction|perc\d+_hu|mean_lung_density|volume_ml)_per_(region|lung)"
+                          r"|local_laa\d+_(mean|sd|p\d+|above\d+)_per_(region|lung)|local_mm|local_window_voxels")
 
 
 def densitometry_from_hist(hist: torch.Tensor, sums: torch.Tensor, spacing: Sequence[float],
@@ -195,6 +196,117 @@ def densitometry_metrics(result: dict, names=None) -> dict:
     cols += [("mean_lung_density", _lst(result["mean_density"]), _lst(lung["mean_density"]), "{:.3f}", float),
              ("volume_ml", _lst(result["volume_ml"]), _lst(lung["volume_ml"]), "{:.1f}", float)]
     return _column_metrics("densitometry_metrics", cols, names)        # a mean of -0.0004 keeps its sign: "-0.000"
+
+
+# --------------------------------------------------------------------------- local LAA map (rides the densitometry section)
+LOCAL_NBINS = 1024                                   # the histogram of the per-mille map: bins 0..1000 hold every value
+_LOCAL_KW = ("n_regions", "threshold", "cuts", "percentiles")
+
+
+def local_laa_params(fn: str, threshold=-950, cuts: Sequence[float] = (0.10, 0.25, 0.50),
+                     percentiles: Sequence[int] = (50, 90)) -> Tuple[int, Tuple[int, ...], Tuple[int, ...]]:
+    """(threshold, cuts in whole per cent, percentiles) of ``local_laa`` as ints; ValueError for a threshold that is no
+    integer in -32768..32768, a cut that is not a whole per cent in 1..100 (given as a fraction: 0.10, 0.25, ...) and a
+    percentile that is no integer in 1..99.  Pure host code."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or int(threshold) != threshold or \
+            not -32768 <= int(threshold) <= 32768:
+        raise ValueError(f"{fn}: threshold must be an integer in -32768..32768, got {threshold!r}")
+    cs = []
+    for c in cuts:
+        pct = round(float(c) * 100.0) if isinstance(c, (int, float)) and not isinstance(c, bool) and math.isfinite(c) else 0
+        if not 1 <= pct <= 100 or abs(float(c) * 100.0 - pct) > 1e-9:
+            raise ValueError(f"{fn}: cuts are fractions of a whole per cent in 0.01..1.00, got {c!r}")
+        cs.append(int(pct))
+    ps = []
+    for p in percentiles:
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or int(p) != p or not 1 <= int(p) <= 99:
+            raise ValueError(f"{fn}: percentiles are integers in 1..99, got {p!r}")
+        ps.append(int(p))
+    return int(threshold), tuple(cs), tuple(ps)
+
+
+def local_laa_from_hist(hist: torch.Tensor, sums: torch.Tensor, cuts: Sequence[float] = (0.10, 0.25, 0.50),
+                        percentiles: Sequence[int] = (50, 90)) -> dict:
+    """The tensor math of ``local_laa``: ``ops.lobe_histogram(map, labels, n, hu_lo=0, nbins=1024)``'s (hist [n+1, nbins],
+    sums [n+1, 2]) int64 of the per-mille map q -> per row 0..n, as fractions (q / 1000):
+      'voxels' [n+1] int64; 'mean' float64 = sum q / (1000 N), both exact integers before the one division; 'sd' float64,
+      the population standard deviation, from the int64 moments sum h_b (b - m) and sum h_b (b - m)^2 about the rounded
+      mean bin m (no cancellation); 'perc' [len(percentiles), n+1] float64: the smallest value whose cumulative count
+      reaches max(1, ceil(p N / 100)) -- the nearest-rank rule of ``densitometry_from_hist``, but bin 0 and bin 1000 are
+      values here, not tails; 'above' [len(cuts), n+1] float64 = #(q >= round(cut * 1000)) / N and 'above_counts' (int64);
+      NaN for a row without voxels; 'whole_lung': the same over the sum of all rows.
+    O(rows * bins) torch operations on the tensors' own device (CPU tensors work), nothing read back."""
+    if hist.dim() != 2 or sums.dim() != 2 or hist.dtype != torch.int64 or sums.dtype != torch.int64 or \
+            hist.shape[0] < 2 or hist.shape[1] < 1001 or tuple(sums.shape) != (hist.shape[0], 2):
+        raise ValueError("local_laa: hist must be int64 [n_regions + 1, nbins >= 1001] and sums int64 [n_regions + 1, 2]")
+    _, cs, ps = local_laa_params("local_laa", -950, cuts, percentiles)
+    h = torch.cat([hist, hist.sum(0, keepdim=True)])       # the last row: the whole lung
+    s = torch.cat([sums, sums.sum(0, keepdim=True)])
+    vox, tot = s[:, 0], s[:, 1]
+    voxd = vox.double()
+    nan = torch.full_like(voxd, float("nan"))
+    some = vox > 0
+    mean = tot.double() / (vox * 1000).double()            # 0 / 0 = NaN for an empty row
+    b = torch.arange(h.shape[1], dtype=torch.int64, device=h.device)
+    m = (2 * tot + vox) // (2 * vox.clamp_min(1))          # the mean bin, rounded
+    d = b[None, :] - m[:, None]
+    m1, m2 = (h * d).sum(1).double() / voxd, (h * d * d).sum(1).double() / voxd
+    sd = torch.where(some, (m2 - m1 * m1).clamp_min(0.0).sqrt() / 1000.0, nan)
+    cdf = h.cumsum(1)
+    perc = torch.full((len(ps), h.shape[0]), float("nan"), dtype=torch.float64, device=h.device)
+    # bin -> fraction, divided on the host: a percentile is then the same float64 on every device
+    value = (torch.arange(h.shape[1], dtype=torch.float64) / 1000.0).to(h.device)
+    for i, p in enumerate(ps):
+        k = ((vox * p + 99) // 100).clamp_min(1)           # nearest rank: max(1, ceil(p N / 100))
+        idx = (cdf < k[:, None]).sum(1)                    # the first bin whose cumulative count reaches k
+        perc[i] = torch.where(some, value[idx.clamp_max(h.shape[1] - 1)], perc[i])
+    counts = torch.stack([vox - cdf[:, 10 * c - 1] for c in cs]) if cs else h.new_zeros((0, h.shape[0]))
+    full = {"voxels": vox, "mean": mean, "sd": sd, "perc": perc, "above": counts.double() / voxd, "above_counts": counts}
+    out = {k: v[..., :-1] for k, v in full.items()}
+    out["whole_lung"] = {k: v[..., -1] for k, v in full.items()}
+    out["cuts"], out["percentiles"] = tuple(c / 100.0 for c in cs), ps
+    return out
+
+
+def local_laa(image: torch.Tensor, labels: torch.Tensor, spacing: Sequence[float], local_mm: float, n_regions: int = 5,
+              threshold: int = -950, cuts: Sequence[float] = (0.10, 0.25, 0.50), percentiles: Sequence[int] = (50, 90),
+              out_u8: Optional[torch.Tensor] = None) -> dict:
+    """The local low-attenuation fraction and its spread per lobe.  image [D,H,W] int16 HU and labels
+    [D,H,W] as ``densitometry`` takes them; spacing (z, y, x) in mm; ``local_mm`` the side of the window in millimetres
+    (``ops.local_window``: a box of 2 r + 1 voxels per axis) -- the caller's choice, like ``cuts``; none is recommended.
+    ``ops.local_fraction3d`` gives the per-mille map q (the share of the lung voxels in the window, of ANY lobe, below
+    ``threshold``; -1 outside the lung), ONE ``ops.lobe_histogram(q, labels, n_regions, hu_lo=0, nbins=1024)`` its exact
+    per-lobe histogram (0..1000 are never clamped; -1 sits only where the label is <= 0, which the histogram does not
+    count), and ``local_laa_from_hist`` the statistics.  -> that function's dict plus 'map' (int16 [D,H,W]), 'radius'
+    (rz, ry, rx), 'local_mm', 'threshold'.  ``out_u8``: ``ops.local_fraction3d``'s, the window of a zero-filled volume on
+    the scan's grid.  ValueError for bad arguments before any device work; device tensors, nothing read back."""
+    t, _, _ = local_laa_params("local_laa", threshold, cuts, percentiles)
+    radius = ops.local_window(spacing, local_mm)
+    n = ops._n_regions("local_laa", n_regions)
+    q = ops.local_fraction3d(image, labels, t, radius, out_u8=out_u8)
+    hist, sums = ops.lobe_histogram(q, labels, n, 0, LOCAL_NBINS)
+    out = local_laa_from_hist(hist, sums, cuts, percentiles)
+    out.update(map=q, radius=radius, local_mm=float(local_mm), threshold=t)
+    return out
+
+
+def local_laa_metrics(result: dict, names=None) -> dict:
+    """``local_laa``'s result -> entries of the metrics dict, keyed like ``densitometry_metrics``: per region
+    'local_laa{|t|}_mean_per_region', '..._sd_...', '..._p{p}_...' per percentile and '..._above{cut in per cent}_...' per
+    cut, all fractions as "{:.3f}", then their whole-lung twins ending '_per_lung', then 'local_mm' ("{:.2f}") and
+    'local_window_voxels' ('{z}x{y}x{x}', the box in voxels).  None (json null) stands for NaN.  Pure host code."""
+    stem = f"local_laa{abs(int(result['threshold']))}"
+    lung = result["whole_lung"]
+    perc, above, lung_perc, lung_above = (_lst(v) for v in (result["perc"], result["above"], lung["perc"], lung["above"]))
+    cols = [(f"{stem}_mean", _lst(result["mean"]), _lst(lung["mean"]), "{:.3f}", float),
+            (f"{stem}_sd", _lst(result["sd"]), _lst(lung["sd"]), "{:.3f}", float)]
+    cols += [(f"{stem}_p{p}", perc[i], lung_perc[i], "{:.3f}", float) for i, p in enumerate(result["percentiles"])]
+    cols += [(f"{stem}_above{int(round(c * 100))}", above[i], lung_above[i], "{:.3f}", float)
+             for i, c in enumerate(result["cuts"])]
+    out = _column_metrics("local_laa_metrics", cols, names)
+    out["local_mm"] = "{:.2f}".format(float(result["local_mm"]))
+    out["local_window_voxels"] = "{}x{}x{}".format(*(2 * int(r) + 1 for r in result["radius"]))
+    return out
 
 
 # --------------------------------------------------------------------------- core / peel split of the per-lobe report
@@ -722,7 +834,8 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
                  densitometry_kw: Optional[dict] = None, core_peel: bool = False, peel_mm: float = 10.0,
                  fissure_mm: Optional[float] = None, clusters: bool = False, cluster_kw: Optional[dict] = None,
                  scan_filter=None,
-                 scan_filter_sections: Sequence[str] = ("densitometry", "core_peel", "clusters"), **prepare_kw) -> dict:
+                 scan_filter_sections: Sequence[str] = ("densitometry", "core_peel", "clusters"),
+                 local_mm: Optional[float] = None, local_kw: Optional[dict] = None, **prepare_kw) -> dict:
     """One scan + its lobe segmentation -> its entry of ``build_outputs``: ``transforms.prepare_case`` (dataset.py:57-92)
     -> ``transforms.prepare_sample(target_size)`` -> a batch of one -> ``module.predict_step`` -> ``build_outputs``.
     The composition only; `prepare_kw` goes to ``prepare_case`` (crop_border, dilate_iterations, ...).  ``regions``:
@@ -778,7 +891,33 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
     sigma_hu in HU) whose taps are confined to the lobe labels, so the median's precondition does not apply either
     (``dilate_iterations=0`` is accepted); the key reads 'bilateral1.00mm60.0hu'.  ValueError, before any device work,
     unless both are finite numbers > 0, for an axis whose radius exceeds 5 (the message names the axis and its spacing)
-    and for a sigma_hu whose range table exceeds 1024 entries (above 289).  No values are recommended."""
+    and for a sigma_hu whose range table exceeds 1024 entries (above 289).  No values are recommended.
+
+    ``local_mm`` (None: off, and the launch sequence, the metrics and 'full_cle' / 'full_pse' are what they are without
+    the argument): the densitometry section gains the local low-attenuation fraction in a window of
+    ``local_mm`` millimetres -- ``local_laa`` on the image that section reads (the filtered one when ``scan_filter`` names
+    'densitometry'), issued directly after the section's own launch; ``local_kw``: n_regions (default: the section's),
+    threshold, cuts, percentiles.  ``local_laa_metrics`` follow the densitometry keys, and the entry gains
+    'full_local_laa': uint8 on the scan's grid like 'full_cle' (255 = the whole window below the threshold), zero outside
+    the lung.  It needs ``densitometry=True``; ValueError, before any device work, without it, for a bad ``local_mm`` or a
+    radius outside 0..16 (the message names the axis and its spacing; all three 0 is refused too), and for an unknown key or
+    a bad value in ``local_kw``.  The arguments never reach ``core_peel``.  No window size or cut is recommended."""
+    local = None
+    if local_mm is not None:
+        if not densitometry:
+            raise ValueError("predict_case: local_mm adds the local LAA map to the densitometry section: it needs "
+                             "densitometry=True")
+        local = dict(local_kw or {})
+        unknown = sorted(set(local) - set(_LOCAL_KW))
+        if unknown:
+            raise ValueError(f"predict_case: local_kw: unknown keys {unknown}; it takes {_LOCAL_KW}")
+        ops.local_window(spacing, local_mm)
+        local_laa_params("predict_case: local_kw", local.get("threshold", -950), local.get("cuts", (0.10, 0.25, 0.50)),
+                         local.get("percentiles", (50, 90)))
+        local.setdefault("n_regions", (densitometry_kw or {}).get("n_regions", 5))
+        ops._n_regions("predict_case: local_kw", local["n_regions"])
+    elif local_kw:
+        raise ValueError("predict_case: local_kw needs local_mm")
     named = tuple(scan_filter_sections)
     for name in named:
         if name not in _SECTIONS or _SECTIONS[name].run is None:
@@ -836,8 +975,13 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
         if name == "clusters" and shapes and core_peel:
             kw[name].update(zones=results["core_peel"]["zones"],
                             zone_names=results["core_peel"].get("zone_names", ZONES))
-        results[name] = _SECTIONS[name].run(smooth if filtered and name in named else case["image"], case["lobe_labels"],
-                                            spacing, **kw[name])
+        source = smooth if filtered and name in named else case["image"]
+        results[name] = _SECTIONS[name].run(source, case["lobe_labels"], spacing, **kw[name])
+        if name == "densitometry" and local is not None:            # rides the section: its image, directly behind it
+            (z0, z1), (y0, y1), (x0, x1) = case["crop_slice"].tolist()
+            full_local = torch.zeros(tuple(case["original_size"].tolist()), dtype=torch.uint8, device=source.device)
+            local_result = local_laa(source, case["lobe_labels"], spacing, local_mm,
+                                     out_u8=full_local[z0:z1, y0:y1, x0:x1], **local)
     cp = results.get("core_peel")
     # core / peel rides the network side on the regions' tail: its zone labels are the batch's labels, with 2n regions
     # (3n with the fissural rind)
@@ -867,6 +1011,9 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
             outside, n = section.outside(results[name])
             if outside > 0:
                 entry["error_messages"].append(section.error.format(outside, n))
+            if name == "densitometry" and local is not None:
+                entry["metrics"].update(local_laa_metrics(local_result, region_names))
+                entry["full_local_laa"] = full_local
     if filtered:
         entry["metrics"]["scan_filter"] = filter_name(scan_filter)
     return entry

@@ -905,6 +905,34 @@ typedef struct DramBilateral {
 int dram_bilateral3d(const int16_t* in, int16_t* out, const void* within, int within_type, long long within_sz,
                      long long within_sy, int D, int H, int W, const DramBilateral* tab, dram_stream_t stream);
 
+/* Local low-attenuation fraction: an exact 3-D box count over the lung (csrc/boxfrac.hip; definitions: INTEGRATION.md
+ * B13).  image [D,H,W] int16 HU, contiguous; labels [D,H,W] of label_dtype 1 (uint8) or 2 (int16), read in place through
+ * stride_z / stride_y (in elements, >= 0; x stride 1) like dram_lobe_hist's; lung = label > 0 (signed for int16).
+ * Per voxel v, with the box B(v) = [z-rz, z+rz] x [y-ry, y+ry] x [x-rx, x+rx] clipped to the volume (voxels outside the
+ * volume count nowhere), each radius in 0..16:
+ *   den(v) = #{u in B(v): label(u) > 0},   num(v) = #{u in B(v): label(u) > 0 and image(u) < threshold}  (strict).
+ *   counts [D,H,W] int32 (or NULL) = num << 16 | den: (2*16+1)^3 = 35 937 < 65 536, both fit their half (the word is
+ *     unsigned in meaning: num = (c >> 16) & 0xffff, which exceeds 32 767 in the largest boxes).
+ *   map [D,H,W] int16: where label(v) > 0 (then den >= 1) q = (2000 num + den) / (2 den), the fraction num / den in per
+ *     mille rounded half up, 0..1000; where label(v) <= 0: -1.
+ *   u8 (or NULL): (q * 255) / 1000, 0 where q = -1, one byte per voxel written at u8[z * u8_stride_z + y * u8_stride_y +
+ *     x]: u8 points at the first voxel of a [D,H,W] window of a larger volume (strides in bytes, >= 0, rows and planes
+ *     of the window disjoint); nothing outside the window is touched.
+ * Every element of counts / map / the u8 window is written; the inputs are only read.  Two launches: the in-plane pass
+ * writes the packed (2ry+1) x (2rx+1) counts of every plane into `work` (dram_boxfrac3d_workspace(D, H, W) = 4 D H W
+ * bytes, 16-byte aligned; work_bytes its size), the z pass walks z with a running sum.  Integers only: exact; 1-D grids,
+ * no atomics, never synchronises, capturable; bit-identical from call to call.
+ * Null image / labels / map / work, label_dtype not 1 / 2, a size < 1, a negative stride, a negative radius, a threshold
+ * outside -32768..32768, outputs that alias an input, the workspace or each other, a u8 window that overlaps itself, a
+ * misaligned pointer, work_bytes too small: DRAM_ERR_BAD_ARG.  A radius above 16, D*H*W >= 2^31: DRAM_ERR_UNSUPPORTED
+ * (the workspace function returns -1). */
+#define DRAM_BOXFRAC_MAX_RADIUS 16
+long long dram_boxfrac3d_workspace(int D, int H, int W);
+int dram_boxfrac3d(const int16_t* image, const void* labels, int label_dtype, long long stride_z, long long stride_y,
+                   int threshold, int rz, int ry, int rx, int32_t* counts, int16_t* map, uint8_t* u8,
+                   long long u8_stride_z, long long u8_stride_y, void* work, long long work_bytes, int D, int H, int W,
+                   dram_stream_t stream);
+
 /* Train-time augmentations (models.py:66-74) with GIVEN parameters, fused into one gather pass:
  * GaussianAddictive (intensity_transforms.py:145-177; noise [D,H,W] supplied by the caller, minmax[2] = volume
  * {min, max} on the device, e.g. folded from dram_minmax partials [nblk][2]), BoxMaskOut (:180-237), Flip
