@@ -187,12 +187,11 @@ extern "C" int dram_boxfrac3d(const int16_t* image, const void* labels, int labe
   {
     DramProf prof(DRAM_FAM_PREP, 29, 0.0, n * (2.0 + label_dtype + 4.0), s);
     const dim3 grid((unsigned)((long long)ntx * nty * D));         // <= D * H * W < 2^31
-    if (label_dtype == 1)
-      hipLaunchKernelGGL((boxfrac_plane_kernel<uint8_t>), grid, dim3(TPB), 0, s, image, (const uint8_t*)labels, sz, sy, mid,
-                         H, W, threshold, ry, rx, ntx, nty, magic);
-    else
-      hipLaunchKernelGGL((boxfrac_plane_kernel<int16_t>), grid, dim3(TPB), 0, s, image, (const int16_t*)labels, sz, sy, mid,
-                         H, W, threshold, ry, rx, ntx, nty, magic);
+    with_label_type(label_dtype, [&](auto t) {
+      using LT = decltype(t);
+      hipLaunchKernelGGL((boxfrac_plane_kernel<LT>), grid, dim3(TPB), 0, s, image, (const LT*)labels, sz, sy, mid, H, W,
+                         threshold, ry, rx, ntx, nty, magic);
+    });
     DRAM_LAUNCH_CHECK();
   }
   {
@@ -201,12 +200,11 @@ extern "C" int dram_boxfrac3d(const int16_t* image, const void* labels, int labe
     const double reads = 2.0 + (2.0 * rz + 1.0) / ZSEG;
     DramProf prof(DRAM_FAM_PREP, 30, 0.0, n * (4.0 * reads + label_dtype + 2.0 + (counts ? 4.0 : 0.0) + (u8 ? 1.0 : 0.0)), s);
     const dim3 grid((unsigned)cdiv(total, ZPB));
-    if (label_dtype == 1)
-      hipLaunchKernelGGL((boxfrac_z_kernel<uint8_t>), grid, dim3(ZPB), 0, s, mid, (const uint8_t*)labels, sz, sy, counts, map,
-                         u8, (long)u8_stride_z, (long)u8_stride_y, D, H, W, rz, total);
-    else
-      hipLaunchKernelGGL((boxfrac_z_kernel<int16_t>), grid, dim3(ZPB), 0, s, mid, (const int16_t*)labels, sz, sy, counts, map,
-                         u8, (long)u8_stride_z, (long)u8_stride_y, D, H, W, rz, total);
+    with_label_type(label_dtype, [&](auto t) {
+      using LT = decltype(t);
+      hipLaunchKernelGGL((boxfrac_z_kernel<LT>), grid, dim3(ZPB), 0, s, mid, (const LT*)labels, sz, sy, counts, map, u8,
+                         (long)u8_stride_z, (long)u8_stride_y, D, H, W, rz, total);
+    });
     DRAM_LAUNCH_CHECK();
   }
   return DRAM_OK;

@@ -287,10 +287,8 @@ extern "C" int dram_label_components(const void* key_or_labels, int lab_elem, lo
     return DRAM_ERR_BAD_ARG;
   if ((long long)D * H * W >= (1LL << 31)) return DRAM_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  return lab_elem == 1 ? run<uint8_t>(key_or_labels, (long)stride_z, (long)stride_y, image, threshold, by_lobe ? 1 : 0,
-                                      connectivity, n_regions, (int*)components, (int*)cluster_voxels,
-                                      (unsigned long long*)table, work, D, H, W, s)
-                       : run<int16_t>(key_or_labels, (long)stride_z, (long)stride_y, image, threshold, by_lobe ? 1 : 0,
-                                      connectivity, n_regions, (int*)components, (int*)cluster_voxels,
-                                      (unsigned long long*)table, work, D, H, W, s);
+  return with_label_type(lab_elem, [&](auto t) {
+    return run<decltype(t)>(key_or_labels, (long)stride_z, (long)stride_y, image, threshold, by_lobe ? 1 : 0, connectivity,
+                            n_regions, (int*)components, (int*)cluster_voxels, (unsigned long long*)table, work, D, H, W, s);
+  });
 }

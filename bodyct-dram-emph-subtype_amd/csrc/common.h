@@ -152,6 +152,10 @@ static inline bool ew_stream(long long tensor_bytes) { return tensor_bytes >= (2
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// The label-volume element type of an entry point (code 1: uint8_t, 2: int16_t; the entry point has checked it):
+// `with_label_type(code, [&](auto t) { using LT = decltype(t); ... })` writes a launch once for both.  Host only.
+template <typename F> static inline auto with_label_type(int code, F&& f) { return code == 1 ? f(uint8_t{}) : f(int16_t{}); }
+
 // XCD-aware bijective remap of the linear workgroup id (8 XCDs, round-robin
 // dispatch): each XCD receives a contiguous run of logical tiles so that
 // neighbouring tiles (which share halo rows / weight panels) hit the same L2.

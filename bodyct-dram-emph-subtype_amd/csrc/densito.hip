@@ -260,12 +260,11 @@ extern "C" int dram_lobe_hist(const void* image, const void* labels, int label_d
   {
     DramProf prof(DRAM_FAM_PREP, 11, 0.0, (double)total * (2.0 + label_dtype) + scratch, s);
     const int img_vec = ((uintptr_t)image & 15) == 0 ? 1 : 0;
-    if (label_dtype == 1)
-      launch_hist<uint8_t>(used, dim3(nblk), s, (const int16_t*)image, labels, (long)stride_z, (long)stride_y, H, W,
-                           (unsigned)total, n_regions, hu_lo, nbins, img_vec, (unsigned*)part_hist, (long long*)part_sums);
-    else
-      launch_hist<int16_t>(used, dim3(nblk), s, (const int16_t*)image, labels, (long)stride_z, (long)stride_y, H, W,
-                           (unsigned)total, n_regions, hu_lo, nbins, img_vec, (unsigned*)part_hist, (long long*)part_sums);
+    with_label_type(label_dtype, [&](auto t) {
+      launch_hist<decltype(t)>(used, dim3(nblk), s, (const int16_t*)image, labels, (long)stride_z, (long)stride_y, H, W,
+                               (unsigned)total, n_regions, hu_lo, nbins, img_vec, (unsigned*)part_hist,
+                               (long long*)part_sums);
+    });
     DRAM_LAUNCH_CHECK();
   }
   DramProf prof(DRAM_FAM_PREP, 12, 0.0, scratch + 8.0 * used + 16.0 * rows, s);

@@ -407,17 +407,13 @@ extern "C" int dram_lobe_zones(const void* labels, int label_dtype, long long st
   if (fissure_um > FULL_UM) fissure_um = FULL_UM;
   hipStream_t s = (hipStream_t)stream;
   const long sz = (long)stride_z, sy = (long)stride_y;
-  if (max_um <= 65535)
-    return label_dtype == 1
-               ? run_lobe<uint8_t, uint32_t>(labels, sz, sy, zones, zone_labels, pleura_mm, fissure_mm_out, workspace, D, H, W,
-                                             sz_um, sy_um, sx_um, peel_um, fissure_um, max_um, n_regions, s)
-               : run_lobe<int16_t, uint32_t>(labels, sz, sy, zones, zone_labels, pleura_mm, fissure_mm_out, workspace, D, H, W,
-                                             sz_um, sy_um, sx_um, peel_um, fissure_um, max_um, n_regions, s);
-  return label_dtype == 1
-             ? run_lobe<uint8_t, uint64_t>(labels, sz, sy, zones, zone_labels, pleura_mm, fissure_mm_out, workspace, D, H, W,
-                                           sz_um, sy_um, sx_um, peel_um, fissure_um, max_um, n_regions, s)
-             : run_lobe<int16_t, uint64_t>(labels, sz, sy, zones, zone_labels, pleura_mm, fissure_mm_out, workspace, D, H, W,
-                                           sz_um, sy_um, sx_um, peel_um, fissure_um, max_um, n_regions, s);
+  auto go = [&](auto d) {                                          // d: the distance word, 32 bits while max_um^2 fits
+    return with_label_type(label_dtype, [&](auto t) {
+      return run_lobe<decltype(t), decltype(d)>(labels, sz, sy, zones, zone_labels, pleura_mm, fissure_mm_out, workspace, D,
+                                                H, W, sz_um, sy_um, sx_um, peel_um, fissure_um, max_um, n_regions, s);
+    });
+  };
+  return max_um <= 65535 ? go(uint32_t{}) : go(uint64_t{});
 }
 
 extern "C" long long dram_lung_zones_workspace(int D, int H, int W, long long max_um) {
@@ -439,13 +435,11 @@ extern "C" int dram_lung_zones(const void* labels, int label_dtype, long long st
   if (peel_um > FULL_UM) peel_um = FULL_UM;
   hipStream_t s = (hipStream_t)stream;
   const long sz = (long)stride_z, sy = (long)stride_y;
-  if (max_um <= 65535)
-    return label_dtype == 1 ? run<uint8_t, uint32_t>(labels, sz, sy, zones, zone_labels, dist_mm, workspace, D, H, W, sz_um,
-                                                     sy_um, sx_um, peel_um, max_um, n_regions, s)
-                            : run<int16_t, uint32_t>(labels, sz, sy, zones, zone_labels, dist_mm, workspace, D, H, W, sz_um,
-                                                     sy_um, sx_um, peel_um, max_um, n_regions, s);
-  return label_dtype == 1 ? run<uint8_t, uint64_t>(labels, sz, sy, zones, zone_labels, dist_mm, workspace, D, H, W, sz_um,
-                                                   sy_um, sx_um, peel_um, max_um, n_regions, s)
-                          : run<int16_t, uint64_t>(labels, sz, sy, zones, zone_labels, dist_mm, workspace, D, H, W, sz_um,
-                                                   sy_um, sx_um, peel_um, max_um, n_regions, s);
+  auto go = [&](auto d) {                                          // d: the distance word, 32 bits while max_um^2 fits
+    return with_label_type(label_dtype, [&](auto t) {
+      return run<decltype(t), decltype(d)>(labels, sz, sy, zones, zone_labels, dist_mm, workspace, D, H, W, sz_um, sy_um,
+                                           sx_um, peel_um, max_um, n_regions, s);
+    });
+  };
+  return max_um <= 65535 ? go(uint32_t{}) : go(uint64_t{});
 }

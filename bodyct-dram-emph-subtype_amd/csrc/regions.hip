@@ -219,12 +219,11 @@ extern "C" int dram_prep_labels(const void* labels, int label_dtype, long long s
   DramProf prof(DRAM_FAM_PREP, 10, 0.0, (double)total * (1.0 + label_dtype), s);
   const dim3 grid(grid_for(total)), block(256);
   const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-  if (label_dtype == 1)
-    hipLaunchKernelGGL((prep_labels_kernel<uint8_t>), grid, block, 0, s, (const uint8_t*)labels, (long)stride_z,
-                       (long)stride_y, zidx, out, D, H, W, Do, Ho, Wo, sy, sx);
-  else
-    hipLaunchKernelGGL((prep_labels_kernel<int16_t>), grid, block, 0, s, (const int16_t*)labels, (long)stride_z,
-                       (long)stride_y, zidx, out, D, H, W, Do, Ho, Wo, sy, sx);
+  with_label_type(label_dtype, [&](auto t) {
+    using LT = decltype(t);
+    hipLaunchKernelGGL((prep_labels_kernel<LT>), grid, block, 0, s, (const LT*)labels, (long)stride_z, (long)stride_y, zidx,
+                       out, D, H, W, Do, Ho, Wo, sy, sx);
+  });
   DRAM_LAUNCH_CHECK();
   return DRAM_OK;
 }

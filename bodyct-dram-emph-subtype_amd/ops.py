@@ -157,6 +157,82 @@ def _label_view(fn: str, t, name: str, like_shape=None):
     return t, (2 if t.dtype == torch.int16 else 1), int(t.stride(0)), int(t.stride(1))
 
 
+def _volume(fn: str, t, name: str, dtypes=None, nonempty: bool = True) -> Tuple[int, int, int]:
+    """The host-only refusals of the [D,H,W] operand ``name`` that a scan-side wrapper reads through a plain pointer: a
+    non-empty 3-D tensor, one of ``dtypes`` (None: left to ``_req`` behind the device check, as ``lobe_histogram`` has
+    it), below 2^31 voxels.  ``nonempty=False`` is ``laa_components``: there an empty image falls to the labels' check.
+    -> (D, H, W) as ints."""
+    if not isinstance(t, Tensor) or t.dim() != 3 or (nonempty and min(t.shape) < 1):
+        raise ValueError(f"{fn}: {name} must be a {'non-empty ' if nonempty else ''}[D,H,W] tensor")
+    if dtypes is not None and t.dtype not in dtypes:
+        kinds = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise TypeError(f"{fn}: expected {'' if name.endswith('s') else 'an '}{kinds} {name}, got {t.dtype}")
+    if t.numel() >= 2 ** 31:
+        raise ValueError(f"{fn}: volumes of 2^31 voxels or more are not supported")
+    return tuple(int(v) for v in t.shape)
+
+
+def _out(fn: str, name: str, t, shape, dtype, device, apart, a: Optional[str] = None,
+         of: Optional[str] = "the image's shape", rest: str = "image"):
+    """The refusals of a caller's output tensor ``name``: its type (``a``: how the message names it), ``shape`` and
+    contiguity in one (``of`` names the shape; None: the shape alone, for ``local_fraction3d``, whose ``out_u8`` is a
+    view), the image's ``device``, and no storage shared with a tensor in ``apart`` (``rest`` names them)."""
+    if not isinstance(t, Tensor) or t.dtype != dtype:
+        raise TypeError(f"{fn}: {name} must be {a or f'a {dtype}'} tensor")
+    if of is None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{fn}: {name} must have the image's shape {tuple(shape)}, got {tuple(t.shape)}")
+    if of is not None and (tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+        raise ValueError(f"{fn}: {name} must be contiguous and of {of} {tuple(shape)}")
+    if t.device != device:
+        raise ValueError(f"{fn}: {name} must live on the image's device")
+    if any(t.untyped_storage().data_ptr() == o.untyped_storage().data_ptr() for o in apart):
+        raise ValueError(f"{fn}: {name} must not share storage with {rest}")
+
+
+def _radius(fn: str, sigma, truncate) -> int:
+    """``int(truncate * sigma + 0.5)``; ValueError in the name of ``fn`` for a negative or non-finite sigma and for
+    ``truncate`` <= 0"""
+    sigma, truncate = float(sigma), float(truncate)
+    if not math.isfinite(sigma) or sigma < 0:
+        raise ValueError(f"{fn}: sigma must be finite and >= 0, got {sigma!r}")
+    if not math.isfinite(truncate) or truncate <= 0:
+        raise ValueError(f"{fn}: truncate must be finite and > 0, got {truncate!r}")
+    return int(truncate * sigma + 0.5)
+
+
+def _sigma3(fn: str, sigma) -> Tuple[float, float, float]:
+    try:
+        sig = [float(v) for v in sigma] if hasattr(sigma, "__len__") or hasattr(sigma, "__iter__") else [float(sigma)] * 3
+    except (TypeError, ValueError):
+        sig = []
+    if len(sig) != 3:
+        raise ValueError(f"{fn}: sigma must be a number or three of them (z, y, x), got {sigma!r}")
+    return tuple(sig)
+
+
+def _spacing3(fn: str, spacing) -> List[float]:
+    """A voxel spacing in mm as three floats (z, y, x); ValueError unless it is three finite numbers > 0"""
+    try:
+        sp = [float(v) for v in spacing]
+    except (TypeError, ValueError):
+        sp = []
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f"{fn}: spacing must be three finite numbers > 0 (z, y, x), got {spacing!r}")
+    return sp
+
+
+def _hu_threshold(fn: str, threshold, noun: str = "an integer", bools: bool = False) -> int:
+    """An LAA threshold as an int: a whole number in -32768..32768 -- one past int16, so that ``image < threshold`` can
+    hold everywhere -- or ValueError; a bool is none, except to ``laa_components`` (``bools``), which always took it"""
+    try:
+        ok = (bools or not isinstance(threshold, bool)) and int(threshold) == threshold and -32768 <= int(threshold) <= 32768
+    except (TypeError, ValueError, OverflowError):                     # None, a string, NaN, inf
+        ok = False
+    if not ok:
+        raise ValueError(f"{fn}: threshold must be {noun} in -32768..32768, got {threshold!r}")
+    return int(threshold)
+
+
 BF16 = torch.bfloat16
 
 
@@ -1391,10 +1467,8 @@ def lobe_histogram(image: Tensor, labels: Tensor, n_regions: int = 5, hu_lo: int
     (n_regions + 1) * nbins <= 32768, hu_lo .. hu_lo + nbins - 1 inside int16, fewer than 2^31 voxels.  Integer counts:
     bit-identical from call to call; never synchronises; every check runs before any launch."""
     n, lo, nb = _n_regions("lobe_histogram", n_regions), int(hu_lo), int(nbins)
-    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
-        raise ValueError("lobe_histogram: image must be a non-empty [D,H,W] tensor")
+    D, H, W = _volume("lobe_histogram", image, "image")
     labels, code, sz, sy = _label_view("lobe_histogram", labels, "labels", image.shape)
-    D, H, W = (int(v) for v in image.shape)
     dev = labels.device
     with launch_scope(dev):
         _req(image, "lobe_histogram: image", torch.int16)
@@ -1418,12 +1492,7 @@ def local_window(spacing, local_mm) -> Tuple[int, int, int]:
     ``local_mm / 2`` is one voxel thick.  ValueError for a spacing or ``local_mm`` that is not positive and finite (or
     rounds to 0 um), for an axis whose radius exceeds 16 (the message names the axis and its spacing) and when all
     three radii are 0: the window would hold one voxel.  Pure host code."""
-    try:
-        sp = [float(v) for v in spacing]
-    except (TypeError, ValueError):
-        sp = []
-    if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
-        raise ValueError(f"local_window: spacing must be three finite numbers > 0 (z, y, x), got {spacing!r}")
+    sp = _spacing3("local_window", spacing)
     if isinstance(local_mm, bool) or not isinstance(local_mm, (int, float)) or not math.isfinite(local_mm) or not local_mm > 0:
         raise ValueError(f"local_window: local_mm must be one finite number > 0, got {local_mm!r}")
     s_um, l_um = [int(round(v * 1000.0)) for v in sp], int(round(float(local_mm) * 1000.0))
@@ -1472,25 +1541,13 @@ def local_fraction3d(image: Tensor, labels: Tensor, threshold: int = -950, radiu
     bit-identical from call to call; the inputs are only read; never synchronises; every check runs before any launch."""
     fn = "local_fraction3d"
     rz, ry, rx = _local_radius(fn, radius)
-    if isinstance(threshold, bool) or int(threshold) != threshold or not -32768 <= int(threshold) <= 32768:
-        raise ValueError(f"{fn}: threshold must be an integer in -32768..32768, got {threshold!r}")
-    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
-        raise ValueError(f"{fn}: image must be a non-empty [D,H,W] tensor")
-    if image.dtype != torch.int16:
-        raise TypeError(f"{fn}: expected an int16 image, got {image.dtype}")
-    D, H, W = (int(v) for v in image.shape)
+    threshold = _hu_threshold(fn, threshold)
+    D, H, W = _volume(fn, image, "image", (torch.int16,))
+    apart = [image] + ([labels] if isinstance(labels, Tensor) else [])
     for name, t, dtype in (("out", out, torch.int16), ("out_u8", out_u8, torch.uint8)):
-        if t is None:
-            continue
-        if not isinstance(t, Tensor) or t.dtype != dtype:
-            raise TypeError(f"{fn}: {name} must be a {dtype} tensor")
-        if tuple(t.shape) != (D, H, W):
-            raise ValueError(f"{fn}: {name} must have the image's shape {(D, H, W)}, got {tuple(t.shape)}")
-        if t.device != image.device:
-            raise ValueError(f"{fn}: {name} must live on the image's device")
-        others = [image] + ([labels] if isinstance(labels, Tensor) else []) + ([out] if t is out_u8 and out is not None else [])
-        if any(t.untyped_storage().data_ptr() == o.untyped_storage().data_ptr() for o in others):
-            raise ValueError(f"{fn}: {name} must not share storage with image, labels or the other output")
+        if t is not None:
+            _out(fn, name, t, (D, H, W), dtype, image.device, apart, of=None, rest="image, labels or the other output")
+            apart.append(t)
     if out is not None and not out.is_contiguous():
         raise ValueError(f"{fn}: out must be contiguous")
     uz = uy = 0
@@ -1514,7 +1571,7 @@ def local_fraction3d(image: Tensor, labels: Tensor, threshold: int = -950, radiu
         if nbytes < 0:
             raise RuntimeError("dram_boxfrac3d_workspace refused the volume")
         ws = _workspace(nbytes, dev)
-        _chk(_L().dram_boxfrac3d(_p(image), _p(labels), code, sz, sy, int(threshold), rz, ry, rx, _p(counts), _p(out),
+        _chk(_L().dram_boxfrac3d(_p(image), _p(labels), code, sz, sy, threshold, rz, ry, rx, _p(counts), _p(out),
                                  _p(out_u8), uz, uy, _p(ws), ws.numel() * 4, D, H, W, _stream()), "dram_boxfrac3d")
     return (out, counts) if want_counts else out
 
@@ -1696,13 +1753,8 @@ def laa_components(image: Tensor, labels: Tensor, threshold: int = -950, n_regio
     of ``densitometry``'s 'laa_counts'), else 0 -- clusters do not cross a fissure, each belongs to one lobe -- or, with
     ``by_lobe=False``, 1 there: whole-lung clusters, reported in row 1 of a table of two rows.  threshold: an integer HU
     in -32768..32768.  -> the triple of ``label_components``."""
-    if not isinstance(image, Tensor) or image.dim() != 3:
-        raise ValueError("laa_components: image must be a [D,H,W] tensor")
-    if image.dtype != torch.int16:
-        raise TypeError(f"laa_components: expected an int16 image, got {image.dtype}")
-    t = int(threshold)
-    if t != threshold or not -32768 <= t <= 32768:
-        raise ValueError(f"laa_components: threshold must be an integer HU in -32768..32768, got {threshold}")
+    _volume("laa_components", image, "image", (torch.int16,), nonempty=False)
+    t = _hu_threshold("laa_components", threshold, "an integer HU", bools=True)
     return _label_components("laa_components", "labels", labels, image, t, bool(by_lobe), connectivity,
                              n_regions if by_lobe else 1, want_sizes)
 
@@ -1736,13 +1788,7 @@ def component_shapes(components: Tensor, labels: Optional[Tensor] = None, zones:
     Fewer than 2^31 voxels.  Integer atomics only: bit-identical from call to call; every check runs before any
     launch."""
     fn = "component_shapes"
-    if not isinstance(components, Tensor) or components.dim() != 3 or min(components.shape) < 1:
-        raise ValueError(f"{fn}: components must be a non-empty [D,H,W] tensor")
-    if components.dtype != torch.int32:
-        raise TypeError(f"{fn}: expected int32 components, got {components.dtype}")
-    if components.numel() >= 2 ** 31:
-        raise ValueError(f"{fn}: volumes of 2^31 voxels or more are not supported")
-    D, H, W = (int(v) for v in components.shape)
+    D, H, W = _volume(fn, components, "components", (torch.int32,))
     if zones is not None:
         if not isinstance(zones, Tensor) or zones.dtype != torch.uint8:
             raise TypeError(f"{fn}: zones must be a uint8 tensor")
@@ -1798,23 +1844,10 @@ def median_filter3d(image: Tensor, size=(3, 3, 3), out: Optional[Tensor] = None)
     min / max selection network on integers: bit-identical from call to call; never synchronises; every check runs
     before any launch."""
     rz, ry, rx = (v // 2 for v in median_size("median_filter3d", size))
-    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
-        raise ValueError("median_filter3d: image must be a non-empty [D,H,W] tensor")
-    if image.dtype != torch.int16:
-        raise TypeError(f"median_filter3d: expected an int16 image, got {image.dtype}")
-    if image.numel() >= 2 ** 31:
-        raise ValueError("median_filter3d: volumes of 2^31 voxels or more are not supported")
+    D, H, W = _volume("median_filter3d", image, "image", (torch.int16,))
     if out is not None:
-        if not isinstance(out, Tensor) or out.dtype != torch.int16:
-            raise TypeError("median_filter3d: out must be an int16 tensor")
-        if tuple(out.shape) != tuple(image.shape) or not out.is_contiguous():
-            raise ValueError(f"median_filter3d: out must be contiguous and of the image's shape {tuple(image.shape)}")
-        if out.device != image.device:
-            raise ValueError("median_filter3d: out must live on the image's device")
-        if out.untyped_storage().data_ptr() == image.untyped_storage().data_ptr():
-            raise ValueError("median_filter3d: out must not share storage with image")
+        _out("median_filter3d", "out", out, (D, H, W), torch.int16, image.device, [image], a="an int16")
     image = image.contiguous()
-    D, H, W = (int(v) for v in image.shape)
     with launch_scope(image.device):
         _req(image, "median_filter3d: image", torch.int16)
         if out is None:
@@ -1829,12 +1862,7 @@ GAUSS_MAX_RADIUS = 16           # DramGaussTaps holds 17 weights per axis
 def gaussian_radius(sigma: float, truncate: float = 4.0) -> int:
     """``int(truncate * sigma + 0.5)``, the radius of the reference's ``generate_gaussian_1d_kernel``
     (functional.py:46).  ValueError for a negative or non-finite sigma and for ``truncate`` <= 0.  Pure host code."""
-    sigma, truncate = float(sigma), float(truncate)
-    if not math.isfinite(sigma) or sigma < 0:
-        raise ValueError(f"gaussian_taps: sigma must be finite and >= 0, got {sigma!r}")
-    if not math.isfinite(truncate) or truncate <= 0:
-        raise ValueError(f"gaussian_taps: truncate must be finite and > 0, got {truncate!r}")
-    return int(truncate * sigma + 0.5)
+    return _radius("gaussian_taps", sigma, truncate)
 
 
 def gaussian_taps(sigma: float, truncate: float = 4.0) -> Tensor:
@@ -1894,23 +1922,12 @@ def gaussian_filter3d(image: Tensor, sigma, truncate: float = 4.0, mode: str = "
     as a list or a host tensor: a device tensor would be read back first); every check runs before any launch."""
     if mode not in ("nearest", "zero"):
         raise ValueError(f"gaussian_filter3d: mode must be 'nearest' or 'zero', got {mode!r}")
-    try:
-        sig = [float(v) for v in sigma] if hasattr(sigma, "__len__") or hasattr(sigma, "__iter__") else [float(sigma)] * 3
-    except (TypeError, ValueError):
-        sig = []
-    if len(sig) != 3:
-        raise ValueError(f"gaussian_filter3d: sigma must be a number or three of them (z, y, x), got {sigma!r}")
     taps = _lib.DramGaussTaps()
-    for a, s in enumerate(sig):
+    for a, s in enumerate(_sigma3("gaussian_filter3d", sigma)):
         half = _gauss_half(s, float(truncate))
         taps.radius[a] = len(half) - 1
         taps.w[a][:len(half)] = half
-    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
-        raise ValueError("gaussian_filter3d: image must be a non-empty [D,H,W] tensor")
-    if image.dtype not in (torch.int16, torch.float32):
-        raise TypeError(f"gaussian_filter3d: expected an int16 or float32 image, got {image.dtype}")
-    if image.numel() >= 2 ** 31:
-        raise ValueError("gaussian_filter3d: volumes of 2^31 voxels or more are not supported")
+    D, H, W = _volume("gaussian_filter3d", image, "image", (torch.int16, torch.float32))
     out_dtype = image.dtype if out_dtype is None else out_dtype
     if out_dtype not in (torch.int16, torch.float32) or (out_dtype == torch.int16 and image.dtype != torch.int16):
         raise TypeError(f"gaussian_filter3d: out_dtype must be float32, or int16 for an int16 image; got {out_dtype} "
@@ -1918,16 +1935,8 @@ def gaussian_filter3d(image: Tensor, sigma, truncate: float = 4.0, mode: str = "
     (z0, z1), (y0, y1), (x0, x1) = _gauss_box(box, image.shape)
     shape = (z1 - z0, y1 - y0, x1 - x0)
     if out is not None:
-        if not isinstance(out, Tensor) or out.dtype != out_dtype:
-            raise TypeError(f"gaussian_filter3d: out must be a {out_dtype} tensor")
-        if tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError(f"gaussian_filter3d: out must be contiguous and of the box's shape {shape}")
-        if out.device != image.device:
-            raise ValueError("gaussian_filter3d: out must live on the image's device")
-        if out.untyped_storage().data_ptr() == image.untyped_storage().data_ptr():
-            raise ValueError("gaussian_filter3d: out must not share storage with image")
+        _out("gaussian_filter3d", "out", out, shape, out_dtype, image.device, [image], of="the box's shape")
     image = image.contiguous()
-    D, H, W = (int(v) for v in image.shape)
     code = {torch.int16: 2, torch.float32: 4}
     with launch_scope(image.device):
         _req(image, "gaussian_filter3d: image", image.dtype)
@@ -1950,12 +1959,7 @@ BILAT_RANGE_LEN = _lib.DRAM_BILAT_RANGE_LEN         # ... and 1024 range entries
 def bilateral_radius(sigma: float, truncate: float = 2.0) -> int:
     """``int(truncate * sigma + 0.5)``, the radius of one axis of ``bilateral_filter3d``.  ValueError for a negative or
     non-finite sigma and for ``truncate`` <= 0.  Pure host code."""
-    sigma, truncate = float(sigma), float(truncate)
-    if not math.isfinite(sigma) or sigma < 0:
-        raise ValueError(f"bilateral_tables: sigma must be finite and >= 0, got {sigma!r}")
-    if not math.isfinite(truncate) or truncate <= 0:
-        raise ValueError(f"bilateral_tables: truncate must be finite and > 0, got {truncate!r}")
-    return int(truncate * sigma + 0.5)
+    return _radius("bilateral_tables", sigma, truncate)
 
 
 @functools.lru_cache(maxsize=64)
@@ -1981,16 +1985,6 @@ def _bilateral_tables(sig: Tuple[float, float, float], sigma_hu: float, truncate
         raise ValueError(f"bilateral_tables: sigma_hu {sigma_hu!r} needs a range table of more than {BILAT_RANGE_LEN} "
                          "entries")
     return spatial[0], spatial[1], spatial[2], tuple(rng)
-
-
-def _sigma3(fn: str, sigma) -> Tuple[float, float, float]:
-    try:
-        sig = [float(v) for v in sigma] if hasattr(sigma, "__len__") or hasattr(sigma, "__iter__") else [float(sigma)] * 3
-    except (TypeError, ValueError):
-        sig = []
-    if len(sig) != 3:
-        raise ValueError(f"{fn}: sigma must be a number or three of them (z, y, x), got {sigma!r}")
-    return tuple(sig)
 
 
 def bilateral_tables(sigma, sigma_hu: float, truncate: float = 2.0):
@@ -2032,28 +2026,15 @@ def bilateral_filter3d(image: Tensor, sigma, sigma_hu: float, truncate: float = 
     it (default: a new one).  -> out.  Nothing outside the volume is read: no border rule.  Fewer than 2^31 voxels.
     One launch, integers only: bit-identical from call to call; never synchronises; every check runs before any launch."""
     tab = _bilateral_struct(_sigma3("bilateral_filter3d", sigma), float(sigma_hu), float(truncate))
-    if not isinstance(image, Tensor) or image.dim() != 3 or min(image.shape) < 1:
-        raise ValueError("bilateral_filter3d: image must be a non-empty [D,H,W] tensor")
-    if image.dtype != torch.int16:
-        raise TypeError(f"bilateral_filter3d: expected an int16 image, got {image.dtype}")
-    if image.numel() >= 2 ** 31:
-        raise ValueError("bilateral_filter3d: volumes of 2^31 voxels or more are not supported")
+    D, H, W = _volume("bilateral_filter3d", image, "image", (torch.int16,))
     if out is not None:
-        if not isinstance(out, Tensor) or out.dtype != torch.int16:
-            raise TypeError("bilateral_filter3d: out must be an int16 tensor")
-        if tuple(out.shape) != tuple(image.shape) or not out.is_contiguous():
-            raise ValueError(f"bilateral_filter3d: out must be contiguous and of the image's shape {tuple(image.shape)}")
-        if out.device != image.device:
-            raise ValueError("bilateral_filter3d: out must live on the image's device")
-        if out.untyped_storage().data_ptr() == image.untyped_storage().data_ptr():
-            raise ValueError("bilateral_filter3d: out must not share storage with image")
+        _out("bilateral_filter3d", "out", out, (D, H, W), torch.int16, image.device, [image], a="an int16")
     code, sz, sy = 0, 0, 0
     if within is not None:
-        within, code, sz, sy = _label_view("bilateral_filter3d", within, "within", tuple(image.shape))
+        within, code, sz, sy = _label_view("bilateral_filter3d", within, "within", (D, H, W))
         if within.device != image.device:
             raise RuntimeError("bilateral_filter3d: within must live on the image's device")
     image = image.contiguous()
-    D, H, W = (int(v) for v in image.shape)
     with launch_scope(image.device):
         _req(image, "bilateral_filter3d: image", torch.int16)
         if out is None:

@@ -208,9 +208,7 @@ def local_laa_params(fn: str, threshold=-950, cuts: Sequence[float] = (0.10, 0.2
     """(threshold, cuts in whole per cent, percentiles) of ``local_laa`` as ints; ValueError for a threshold that is no
     integer in -32768..32768, a cut that is not a whole per cent in 1..100 (given as a fraction: 0.10, 0.25, ...) and a
     percentile that is no integer in 1..99.  Pure host code."""
-    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or int(threshold) != threshold or \
-            not -32768 <= int(threshold) <= 32768:
-        raise ValueError(f"{fn}: threshold must be an integer in -32768..32768, got {threshold!r}")
+    threshold = ops._hu_threshold(fn, threshold)
     cs = []
     for c in cuts:
         pct = round(float(c) * 100.0) if isinstance(c, (int, float)) and not isinstance(c, bool) and math.isfinite(c) else 0
@@ -222,7 +220,7 @@ def local_laa_params(fn: str, threshold=-950, cuts: Sequence[float] = (0.10, 0.2
         if isinstance(p, bool) or not isinstance(p, (int, float)) or int(p) != p or not 1 <= int(p) <= 99:
             raise ValueError(f"{fn}: percentiles are integers in 1..99, got {p!r}")
         ps.append(int(p))
-    return int(threshold), tuple(cs), tuple(ps)
+    return threshold, tuple(cs), tuple(ps)
 
 
 def local_laa_from_hist(hist: torch.Tensor, sums: torch.Tensor, cuts: Sequence[float] = (0.10, 0.25, 0.50),
@@ -661,34 +659,42 @@ def filtered_image(case_image: torch.Tensor, size=(3, 3, 3)) -> torch.Tensor:
     return ops.median_filter3d(case_image, size)
 
 
+def _tagged_numbers(fn: str, scan_filter, tag: str, count: int, says: str) -> Optional[Tuple[float, ...]]:
+    """the ``count`` numbers behind the string ``tag``; None without the tag; ValueError (``says``) for any other numbers"""
+    if not isinstance(scan_filter, (tuple, list)) or len(scan_filter) < 1 or scan_filter[0] != tag:
+        return None
+    if len(scan_filter) != count + 1 or not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+                                                 and v > 0 for v in scan_filter[1:]):
+        raise ValueError(f"{fn}: {says}, got {scan_filter!r}")
+    return tuple(float(v) for v in scan_filter[1:])
+
+
 def gaussian_sigma_mm(fn: str, scan_filter) -> Optional[float]:
     """The sigma in millimetres of a ``("gaussian", sigma_mm)`` scan filter; None for anything that does not start with
     the string 'gaussian' (a median window size).  ValueError unless sigma_mm is one finite number > 0.  Pure host code."""
-    if not isinstance(scan_filter, (tuple, list)) or len(scan_filter) < 1 or scan_filter[0] != "gaussian":
-        return None
-    ok = len(scan_filter) == 2 and isinstance(scan_filter[1], (int, float)) and not isinstance(scan_filter[1], bool)
-    if not ok or not math.isfinite(scan_filter[1]) or not scan_filter[1] > 0:
-        raise ValueError(f"{fn}: a Gaussian scan filter is ('gaussian', sigma_mm) with a finite sigma_mm > 0, got "
-                         f"{scan_filter!r}")
-    return float(scan_filter[1])
+    p = _tagged_numbers(fn, scan_filter, "gaussian", 1,
+                        "a Gaussian scan filter is ('gaussian', sigma_mm) with a finite sigma_mm > 0")
+    return None if p is None else p[0]
 
 
-def gaussian_sigma_voxels(fn: str, spacing: Sequence[float], sigma_mm: float) -> Tuple[float, float, float]:
-    """sigma_mm / spacing per axis (z, y, x), in Python floats.  ValueError, naming the axis and its spacing, when the
-    radius ``int(4 sigma + 0.5)`` of an axis exceeds the 16 the filter holds; an axis whose radius is 0 (slices much
-    thicker than sigma) is left untouched by the filter.  Pure host code."""
-    sp = [float(v) for v in spacing]
-    if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
-        raise ValueError(f"{fn}: spacing must be three finite numbers > 0 (z, y, x), got {tuple(spacing)!r}")
+def sigma_voxels(fn: str, spacing, sigma_mm: float, radius_of: Callable, max_radius: int) -> Tuple[float, float, float]:
+    """sigma_mm / spacing per axis (z, y, x) as Python floats.  ValueError, naming the axis and its spacing, when an axis'
+    radius ``radius_of(sigma)`` exceeds ``max_radius``; radius 0 (slices much thicker than sigma): the axis is untouched."""
+    sp = ops._spacing3(fn, spacing)
     if not (math.isfinite(sigma_mm) and sigma_mm > 0):
         raise ValueError(f"{fn}: sigma_mm must be finite and > 0, got {sigma_mm!r}")
     sig = tuple(float(sigma_mm) / v for v in sp)
     for axis, s, v in zip("zyx", sig, sp):
-        r = ops.gaussian_radius(s)
-        if r > ops.GAUSS_MAX_RADIUS:
+        r = radius_of(s)
+        if r > max_radius:
             raise ValueError(f"{fn}: sigma {sigma_mm} mm on axis {axis} with spacing {v} mm is {s:.2f} voxels, radius "
-                             f"{r}; the filter holds radius <= {ops.GAUSS_MAX_RADIUS}")
+                             f"{r}; the filter holds radius <= {max_radius}")
     return sig
+
+
+def gaussian_sigma_voxels(fn: str, spacing: Sequence[float], sigma_mm: float) -> Tuple[float, float, float]:
+    """``sigma_voxels`` under the Gaussian filter's cap: the radius ``int(4 sigma + 0.5)`` of an axis is at most 16."""
+    return sigma_voxels(fn, spacing, sigma_mm, ops.gaussian_radius, ops.GAUSS_MAX_RADIUS)
 
 
 def gaussian_image(scan: torch.Tensor, crop_slice, spacing: Sequence[float], sigma_mm: float) -> torch.Tensor:
@@ -705,32 +711,13 @@ def gaussian_image(scan: torch.Tensor, crop_slice, spacing: Sequence[float], sig
 def bilateral_params(fn: str, scan_filter) -> Optional[Tuple[float, float]]:
     """(sigma_mm, sigma_hu) of a ``("bilateral", sigma_mm, sigma_hu)`` scan filter; None for anything that does not
     start with the string 'bilateral'.  ValueError unless both are finite numbers > 0 (no bools).  Pure host code."""
-    if not isinstance(scan_filter, (tuple, list)) or len(scan_filter) < 1 or scan_filter[0] != "bilateral":
-        return None
-    ok = len(scan_filter) == 3 and all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
-                                       and v > 0 for v in scan_filter[1:])
-    if not ok:
-        raise ValueError(f"{fn}: a bilateral scan filter is ('bilateral', sigma_mm, sigma_hu) with finite sigma_mm > 0 "
-                         f"and sigma_hu > 0, got {scan_filter!r}")
-    return float(scan_filter[1]), float(scan_filter[2])
+    return _tagged_numbers(fn, scan_filter, "bilateral", 2, "a bilateral scan filter is ('bilateral', sigma_mm, sigma_hu) "
+                           "with finite sigma_mm > 0 and sigma_hu > 0")
 
 
 def bilateral_sigma_voxels(fn: str, spacing: Sequence[float], sigma_mm: float) -> Tuple[float, float, float]:
-    """sigma_mm / spacing per axis (z, y, x), in Python floats, as ``gaussian_sigma_voxels`` forms it.  ValueError,
-    naming the axis and its spacing, when the radius ``int(2 sigma + 0.5)`` of an axis exceeds the 5 the bilateral
-    filter holds; an axis whose radius is 0 is left untouched by the filter.  Pure host code."""
-    sp = [float(v) for v in spacing]
-    if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
-        raise ValueError(f"{fn}: spacing must be three finite numbers > 0 (z, y, x), got {tuple(spacing)!r}")
-    if not (math.isfinite(sigma_mm) and sigma_mm > 0):
-        raise ValueError(f"{fn}: sigma_mm must be finite and > 0, got {sigma_mm!r}")
-    sig = tuple(float(sigma_mm) / v for v in sp)
-    for axis, s, v in zip("zyx", sig, sp):
-        r = ops.bilateral_radius(s)
-        if r > ops.BILAT_MAX_RADIUS:
-            raise ValueError(f"{fn}: sigma {sigma_mm} mm on axis {axis} with spacing {v} mm is {s:.2f} voxels, radius "
-                             f"{r}; the filter holds radius <= {ops.BILAT_MAX_RADIUS}")
-    return sig
+    """``sigma_voxels`` under the bilateral filter's cap: the radius ``int(2 sigma + 0.5)`` of an axis is at most 5."""
+    return sigma_voxels(fn, spacing, sigma_mm, ops.bilateral_radius, ops.BILAT_MAX_RADIUS)
 
 
 def bilateral_image(case_image: torch.Tensor, lobe_labels: torch.Tensor, spacing: Sequence[float], sigma_mm: float,
@@ -745,16 +732,45 @@ def bilateral_image(case_image: torch.Tensor, lobe_labels: torch.Tensor, spacing
     return ops.bilateral_filter3d(case_image, sig, float(sigma_hu), within=lobe_labels)
 
 
+class _ScanFilter(NamedTuple):
+    """One kind of ``predict_case``'s ``scan_filter``.  A new filter is one record in ``_SCAN_FILTERS`` (plus its kernel)."""
+    parse: Callable         # (fn, scan_filter) -> its parameters, or None: not this kind; ValueError for bad ones
+    check: Callable         # (fn, params, spacing, prepare_kw): everything that is refused before device work
+    image: Callable         # (params, scan, case, spacing) -> the filtered int16 image of the case; device work only
+    name: Callable          # params -> the report's 'scan_filter' value
+
+
+def _median_needs(fn: str, size, spacing, prepare_kw):
+    if int(prepare_kw.get("dilate_iterations", 2)) < 1 or not prepare_kw.get("crop_border", 5) > 0:
+        raise ValueError(f"{fn} needs dilate_iterations >= 1 and crop_border > 0: without them a window centred on a "
+                         "lung voxel reaches the fill value or the crop's edge")
+
+
+_SCAN_FILTERS = {       # asked in this order: the median, which takes whatever carries no name, comes last
+    "bilateral": _ScanFilter(                               # its check: the radius cap per axis, the range table's cap
+        bilateral_params, lambda fn, p, spacing, kw: ops.bilateral_tables(bilateral_sigma_voxels(fn, spacing, p[0]), p[1]),
+        lambda p, scan, case, spacing: bilateral_image(case["image"], case["lobe_labels"], spacing, *p),
+        lambda p: "bilateral{:.2f}mm{:.1f}hu".format(*p)),
+    "gaussian": _ScanFilter(
+        gaussian_sigma_mm, lambda fn, p, spacing, kw: gaussian_sigma_voxels(fn, spacing, p),      # the radius cap, per axis
+        lambda p, scan, case, spacing: gaussian_image(scan, case["crop_slice"], spacing, p), "gaussian{:.2f}mm".format),
+    "median": _ScanFilter(
+        ops.median_size, _median_needs, lambda p, scan, case, spacing: filtered_image(case["image"], p),
+        lambda p: "median{}x{}x{}".format(*p)),
+}
+
+
+def _scan_filter(fn: str, scan_filter) -> Tuple[_ScanFilter, object]:
+    """(record, parameters) of a ``scan_filter`` value; ValueError in the name of ``fn`` for one that is no filter"""
+    asked = ((record, record.parse(fn, scan_filter)) for record in _SCAN_FILTERS.values())
+    return next((record, params) for record, params in asked if params is not None)
+
+
 def filter_name(size) -> str:
     """The value of the report's 'scan_filter' key: 'median{z}x{y}x{x}' of a median window size, 'gaussian{:.2f}mm' of
     ``("gaussian", sigma_mm)``, 'bilateral{:.2f}mm{:.1f}hu' of ``("bilateral", sigma_mm, sigma_hu)``."""
-    bilateral = bilateral_params("filter_name", size)
-    if bilateral is not None:
-        return "bilateral{:.2f}mm{:.1f}hu".format(*bilateral)
-    sigma_mm = gaussian_sigma_mm("filter_name", size)
-    if sigma_mm is not None:
-        return "gaussian{:.2f}mm".format(sigma_mm)
-    return "median{}x{}x{}".format(*ops.median_size("filter_name", size))
+    record, params = _scan_filter("filter_name", size)
+    return record.name(params)
 
 
 # --------------------------------------------------------------------------- the sections of the report
@@ -912,8 +928,7 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
         if unknown:
             raise ValueError(f"predict_case: local_kw: unknown keys {unknown}; it takes {_LOCAL_KW}")
         ops.local_window(spacing, local_mm)
-        local_laa_params("predict_case: local_kw", local.get("threshold", -950), local.get("cuts", (0.10, 0.25, 0.50)),
-                         local.get("percentiles", (50, 90)))
+        local_laa_params("predict_case: local_kw", **{k: v for k, v in local.items() if k != "n_regions"})
         local.setdefault("n_regions", (densitometry_kw or {}).get("n_regions", 5))
         ops._n_regions("predict_case: local_kw", local["n_regions"])
     elif local_kw:
@@ -923,20 +938,9 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
         if name not in _SECTIONS or _SECTIONS[name].run is None:
             raise ValueError(f"predict_case: scan_filter_sections: {name!r} is not a scan-side section "
                              f"{tuple(k for k, v in _SECTIONS.items() if v.run is not None)}")
-    sigma_mm = gaussian_sigma_mm("predict_case: scan_filter", scan_filter)
-    bilateral = bilateral_params("predict_case: scan_filter", scan_filter)
-    if bilateral is not None:
-        sig = bilateral_sigma_voxels("predict_case: scan_filter", spacing, bilateral[0])    # the radius cap, per axis
-        ops.bilateral_tables(sig, bilateral[1])                                             # the range table's cap
-        scan_filter = ("bilateral",) + bilateral
-    elif sigma_mm is not None:
-        gaussian_sigma_voxels("predict_case: scan_filter", spacing, sigma_mm)       # the radius cap, per axis
-        scan_filter = ("gaussian", sigma_mm)
-    elif scan_filter is not None:
-        scan_filter = ops.median_size("predict_case: scan_filter", scan_filter)
-        if int(prepare_kw.get("dilate_iterations", 2)) < 1 or not prepare_kw.get("crop_border", 5) > 0:
-            raise ValueError("predict_case: scan_filter needs dilate_iterations >= 1 and crop_border > 0: without them a "
-                             "window centred on a lung voxel reaches the fill value or the crop's edge")
+    if scan_filter is not None:
+        noise_filter, filter_params = _scan_filter("predict_case: scan_filter", scan_filter)
+        noise_filter.check("predict_case: scan_filter", filter_params, spacing, prepare_kw)
     on = {"regions": bool(regions), "densitometry": bool(densitometry), "core_peel": bool(core_peel),
           "clusters": bool(clusters)}
     kw = {"densitometry": dict(densitometry_kw or {}), "clusters": dict(cluster_kw or {})}
@@ -956,12 +960,7 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
                              "for another count")
     case = transforms.prepare_case(scan, lobes, spacing, uid=uid, want_lobes=any(on.values()), **prepare_kw)
     filtered = scan_filter is not None and any(on[name] for name in named)
-    if filtered and bilateral is not None:
-        smooth = bilateral_image(case["image"], case["lobe_labels"], spacing, *bilateral)
-    elif filtered and sigma_mm is not None:
-        smooth = gaussian_image(scan, case["crop_slice"], spacing, sigma_mm)
-    else:
-        smooth = filtered_image(case["image"], scan_filter) if filtered else None
+    smooth = noise_filter.image(filter_params, scan, case, spacing) if filtered else None
     order = _LAUNCH_ORDER
     shapes = on["clusters"] and bool(kw["clusters"].get("shapes"))
     if shapes:
@@ -1015,7 +1014,7 @@ def predict_case(module, scan: torch.Tensor, lobes: torch.Tensor, spacing: Seque
                 entry["metrics"].update(local_laa_metrics(local_result, region_names))
                 entry["full_local_laa"] = full_local
     if filtered:
-        entry["metrics"]["scan_filter"] = filter_name(scan_filter)
+        entry["metrics"]["scan_filter"] = noise_filter.name(filter_params)
     return entry
 
 
