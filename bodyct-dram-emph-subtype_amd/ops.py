@@ -17,7 +17,7 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -495,13 +495,64 @@ _PLAN_ENV = ("DRAM_CONV_ALGO", "DRAM_WINO_TILING", "DRAM_MATH", "DRAM_W2D_V", "D
              "DRAM_WGRAD_V", "DRAM_BF16_NW", "DRAM_BF16_WGRAD", "DRAM_NN_STREAM")
 
 
+class _ConvAlgo(NamedTuple):
+    """One forward / data-gradient algorithm: what a caller has to know to pack for it and to launch it."""
+    family: str                 # profiler family of its launches
+    rows: str                   # query: rows of the forward's statistics
+    points: object              # leading dimension of the packed wf and wb: None the kernel's taps, or the (wf, wb) queries
+    pack: str                   # (w, wf, wb, ...
+    pack_ints: int              # ... the first so many of Cout, Cin, taps -- none of them: the desc -- and the stream)
+    fwd: str                    # (x, wf, bias, y, stats, ...
+    bwd: str                    # (dy, wb, dx, add, gate, ...
+    ws: bool = False            # ... v, desc, ws, nbytes, stream) with the plan's ws_fwd / ws_bwd, else ... desc, stream)
+    rows_bwd: Optional[str] = None      # query: rows of the statistics its data gradient can take along
+
+
+class _WgradAlgo(NamedTuple):
+    """One weight-gradient algorithm: (x, [v_cache,] dy, dw, desc, ws, nbytes, stream)."""
+    family: str
+    fn: str
+    workspace: tuple            # query of its workspace bytes, and what it takes behind the desc
+    v_cache: bool = False       # takes the forward's transformed input, and can run from it alone
+    min_ws: int = 0             # scratch to hold even where the plan asks for none
+
+    def ws_bytes(self, L, d) -> int:
+        return int(getattr(L, self.workspace[0])(d, *self.workspace[1:]))
+
+
+# dram_conv_algo's answers, and the bf16-storage kernels (ConvPlan.bf16: 3x3x3 stride 1 and 1x1x1)
+_CONV_ALGOS = {
+    0: _ConvAlgo("conv_igemm_kernel", "dram_conv_num_mtiles", None, "dram_pack_conv_weight", 3,
+                 "dram_conv3d_fwd", "dram_conv3d_bwd_data"),
+    1: _ConvAlgo("conv_wino_kernels", "dram_wino_num_stat_rows", ("dram_wino_num_points", "dram_wino_num_points_bwd"),
+                 "dram_wino_pack_weight", 0, "dram_wino_conv3d_fwd", "dram_wino_conv3d_bwd_data", ws=True,
+                 rows_bwd="dram_wino_num_stat_rows_bwd"),
+    2: _ConvAlgo("conv_wino2d_kernel", "dram_wino2d_num_stat_rows", 48, "dram_wino2d_pack_weight", 2,
+                 "dram_wino2d_conv3d_fwd", "dram_wino2d_conv3d_bwd_data"),
+    3: _ConvAlgo("conv1x1_gemm", "dram_conv1x1_num_stat_rows", None, "dram_pack_conv_weight", 3,      # wf IS the weight
+                 "dram_conv1x1_fwd", "dram_conv1x1_bwd_data"),
+    BF16: _ConvAlgo("conv3_bf16_kernel", "dram_conv_bf16_num_stat_rows", None, "dram_pack_conv_weight_bf16", 3,
+                    "dram_conv3d_fwd_bf16", "dram_conv3d_bwd_data_bf16"),
+}
+# dram_conv_wgrad_algo's answers, and the bf16-storage kernel
+_WGRAD_ALGOS = {
+    0: _WgradAlgo("conv_wgrad_kernel+reduce", "dram_conv3d_bwd_weight", ("dram_conv3d_bwd_weight_workspace",)),
+    1: _WgradAlgo("conv_wino_kernels", "dram_wino_conv3d_bwd_weight", ("dram_wino_workspace", 2), v_cache=True),
+    2: _WgradAlgo("conv_wgrad_w2d_kernel+reduce", "dram_wgrad_w2d", ("dram_wgrad_w2d_workspace",)),
+    3: _WgradAlgo("conv1x1_gemm", "dram_conv1x1_bwd_weight", ("dram_conv1x1_bwd_weight_workspace",), min_ws=4),
+    BF16: _WgradAlgo("wgrad3_bf16_kernel+reduce", "dram_conv3d_bwd_weight_bf16", ("dram_conv3d_bwd_weight_bf16_workspace",)),
+}
+
+
 class ConvPlan:
     """Everything the host needs to know about one convolution geometry, asked from the library ONCE per
-    (geometry, plan-relevant environment): forward / weight-gradient algorithm, packed-weight leading
-    dimensions, statistic rows, workspace sizes, cached-transform size -- ~12 host calls into the library
-    (each of which re-derives tilings and reads the environment) instead of that many per launch."""
-    __slots__ = ("desc", "dref", "desc_ovl", "dref_ovl", "algo", "walgo", "taps_f", "taps_b", "stat_rows", "ws_fwd", "ws_bwd", "ws_wgrad",
-                 "v_elems", "ws_direct_wgrad", "bf16", "bf16_stat_rows", "bf16_ws_wgrad", "prologue")
+    (geometry, plan-relevant environment): forward / weight-gradient algorithm (the rows of _CONV_ALGOS / _WGRAD_ALGOS
+    its launches go through), packed-weight leading dimensions, statistic rows, workspace sizes, cached-transform
+    size -- ~12 host calls into the library (each of which re-derives tilings and reads the environment) instead of
+    that many per launch."""
+    __slots__ = ("desc", "dref", "desc_ovl", "dref_ovl", "algo", "walgo", "conv", "wgrad", "taps_f", "taps_b", "stat_rows",
+                 "stat_rows_bwd", "ws_fwd", "ws_bwd", "ws_wgrad", "wgrad_from_v", "v_elems", "bf16", "bf16_stat_rows",
+                 "bf16_ws_wgrad", "prologue")
 
     def __init__(self, g: "ConvGeom"):
         L = _L()
@@ -514,26 +565,29 @@ class ConvPlan:
         self.dref_ovl = ctypes.byref(self.desc_ovl)
         self.algo = int(L.dram_conv_algo(d))
         self.walgo = int(L.dram_conv_wgrad_algo(d))
-        if self.algo == 1:
-            self.taps_f, self.taps_b = int(L.dram_wino_num_points(d)), int(L.dram_wino_num_points_bwd(d))
-        else:
-            self.taps_f = self.taps_b = 48 if self.algo == 2 else g.taps
-        self.stat_rows = int({0: L.dram_conv_num_mtiles, 1: L.dram_wino_num_stat_rows, 2: L.dram_wino2d_num_stat_rows,
-                              3: L.dram_conv1x1_num_stat_rows}[self.algo](d))
-        self.ws_fwd = int(L.dram_wino_workspace(d, 0)) if self.algo == 1 else 0
-        self.ws_bwd = int(L.dram_wino_workspace(d, 1)) if self.algo == 1 else 0
-        self.v_elems = int(L.dram_wino_v_elems(d)) if (self.algo == 1 or self.walgo == 1) else 0
-        self.ws_wgrad = {3: lambda: int(L.dram_conv1x1_bwd_weight_workspace(d)),
-                         2: lambda: int(L.dram_wgrad_w2d_workspace(d)),
-                         1: lambda: int(L.dram_wino_workspace(d, 2))}.get(self.walgo, lambda: 0)()
-        self.ws_direct_wgrad = int(L.dram_conv3d_bwd_weight_workspace(d)) if (self.walgo == 0 or self.ws_wgrad == 0) else 0
+        conv = self.conv = _CONV_ALGOS[self.algo]
+        pts = conv.points
+        self.taps_f, self.taps_b = [int(getattr(L, q)(d)) for q in pts] if isinstance(pts, tuple) else [pts or g.taps] * 2
+        self.stat_rows = int(getattr(L, conv.rows)(d))
+        self.stat_rows_bwd = int(getattr(L, conv.rows_bwd)(d)) if conv.rows_bwd else 0
+        self.ws_fwd, self.ws_bwd = (int(L.dram_wino_workspace(d, 0)), int(L.dram_wino_workspace(d, 1))) if conv.ws else (0, 0)
+        # the weight gradient that RUNS: a pipeline geometry whose TN plan fails reports no workspace and stays on the
+        # direct kernel (which needs the input tensor itself)
+        self.wgrad = _WGRAD_ALGOS[self.walgo]
+        self.v_elems = int(L.dram_wino_v_elems(d)) if (conv.ws or self.wgrad.v_cache) else 0
+        self.ws_wgrad = self.wgrad.ws_bytes(L, d)
+        if self.wgrad.v_cache and not self.ws_wgrad:
+            self.wgrad = _WGRAD_ALGOS[0]
+            self.ws_wgrad = self.wgrad.ws_bytes(L, d)
+        # can conv3d_bwd_weight run from the forward's cached Winograd-domain input alone (x=None, v_cache=...)?
+        self.wgrad_from_v = self.wgrad.v_cache
         # bf16-storage path: the direct bf16-MFMA kernels take the 3x3x3 stride-1 and the 1x1x1 convolutions; the one
         # stride-2 convolution per network runs on them through its space-to-depth form (s2_geom), whatever is left
-        # (odd extents) on the fp32 kernels above around cast passes
-        self.prologue = bool(self.algo == 1 and L.dram_wino_prologue_supported(d))
+        # (odd extents) on the fp32 kernels above around cast passes (bf16_route)
+        self.prologue = bool(conv.ws and L.dram_wino_prologue_supported(d))
         self.bf16 = bool(L.dram_conv_bf16_supported(d))
-        self.bf16_stat_rows = int(L.dram_conv_bf16_num_stat_rows(d)) if self.bf16 else 0
-        self.bf16_ws_wgrad = int(L.dram_conv3d_bwd_weight_bf16_workspace(d)) if self.bf16 else 0
+        self.bf16_stat_rows = int(getattr(L, _CONV_ALGOS[BF16].rows)(d)) if self.bf16 else 0
+        self.bf16_ws_wgrad = _WGRAD_ALGOS[BF16].ws_bytes(L, d) if self.bf16 else 0
 
 
 _PLANS: Dict[tuple, ConvPlan] = {}
@@ -560,13 +614,6 @@ def conv_use_wino(g: "ConvGeom") -> bool:
     return conv_algo(g) == 1
 
 
-def packed_taps(g: "ConvGeom", bwd: bool = False) -> int:
-    """Leading dimension of the packed weights the library's plan expects for g (forward operand wf, or
-    with bwd=True the data-gradient operand wb: the Winograd pipeline may tile the two passes differently)."""
-    p = conv_plan(g)
-    return p.taps_b if bwd else p.taps_f
-
-
 def s2_geom(g: "ConvGeom") -> Optional["ConvGeom"]:
     """bf16 storage: the stride-1 geometry that runs a stride-2 3x3x3 convolution on the bf16 kernels (space to depth:
     eight parity sub-lattices as 8 Cin channels at half the extents, embedded weights -- include/dram_hip.h,
@@ -585,6 +632,23 @@ def s2d(x: Tensor) -> Tensor:
     return x8
 
 
+def bf16_route(g: "ConvGeom", plan: ConvPlan, w: Optional[Tensor] = None, cin_axis: int = 2
+               ) -> Tuple[str, Optional["ConvGeom"]]:
+    """How a convolution (g, its plan) runs on bf16 activations -> (route, the geometry its kernels are launched for):
+    "native" the bf16 kernels on g; "s2d" stride 2 as stride 1 over the space-to-depth tensor (s2_geom(g)); "casts" the
+    fp32 kernels around cast passes.  A pass with a weight operand runs what `w` was packed for (its type, and the
+    8 * Cin channels of the embedded weights on `cin_axis`); pack_conv_weight and the weight gradient, which have none,
+    ask the plan and then s2_geom."""
+    if w is not None:
+        if w.dtype != BF16:
+            return "casts", g
+        return ("s2d", s2_geom(g)) if w.shape[cin_axis] == 8 * g.Cin else ("native", g)
+    if plan.bf16:
+        return "native", g
+    g8 = s2_geom(g)
+    return ("casts", g) if g8 is None else ("s2d", g8)
+
+
 def pack_conv_weight(w: Tensor, want_fwd=True, want_bwd=True, g: Optional["ConvGeom"] = None, dtype=torch.float32
                      ) -> Tuple[Optional[Tensor], Optional[Tensor]]:
     """[Cout,Cin,k,k,k] -> wf [taps,Cout,Cin], wb [taps,Cin,Cout]; for a geometry the library plans
@@ -594,32 +658,21 @@ def pack_conv_weight(w: Tensor, want_fwd=True, want_bwd=True, g: Optional["ConvG
     _req(w, "w")
     Cout, Cin = w.shape[0], w.shape[1]
     taps = w.shape[2] * w.shape[3] * w.shape[4]
-    if dtype == BF16 and g is not None and conv_plan(g).bf16:
-        wf = torch.empty((taps, Cout, Cin), device=w.device, dtype=BF16) if want_fwd else None
-        wb = torch.empty((taps, Cin, Cout), device=w.device, dtype=BF16) if want_bwd else None
-        _chk(_L().dram_pack_conv_weight_bf16(_p(w), _p(wf), _p(wb), Cout, Cin, taps, _stream()), "dram_pack_conv_weight_bf16")
-        return wf, wb
-    if dtype == BF16 and g is not None and s2_geom(g) is not None:      # stride 2: embedded weights of the stride-1 form
-        w3 = torch.empty((Cout, 8 * Cin, 3, 3, 3), device=w.device, dtype=torch.float32)
-        _chk(_L().dram_s2_embed_weight(_p(w), _p(w3), Cout, Cin, _stream()), "dram_s2_embed_weight")
-        wf = torch.empty((taps, Cout, 8 * Cin), device=w.device, dtype=BF16) if want_fwd else None
-        wb = torch.empty((taps, 8 * Cin, Cout), device=w.device, dtype=BF16) if want_bwd else None
-        _chk(_L().dram_pack_conv_weight_bf16(_p(w3), _p(wf), _p(wb), Cout, 8 * Cin, taps, _stream()),
-             "dram_pack_conv_weight_bf16")
-        return wf, wb
     plan = conv_plan(g) if g is not None else None
-    algo = plan.algo if plan else 0
-    pt = plan.taps_f if plan else taps
-    ptb = plan.taps_b if plan else taps
-    wf = torch.empty((pt, Cout, Cin), device=w.device, dtype=torch.float32) if want_fwd else None
-    wb = torch.empty((ptb, Cin, Cout), device=w.device, dtype=torch.float32) if want_bwd else None
-    if algo == 1:
-        _chk(_L().dram_wino_pack_weight(_p(w), _p(wf), _p(wb), plan.dref, _stream()),
-             "dram_wino_pack_weight")
-    elif algo == 2:
-        _chk(_L().dram_wino2d_pack_weight(_p(w), _p(wf), _p(wb), Cout, Cin, _stream()), "dram_wino2d_pack_weight")
+    route = bf16_route(g, plan)[0] if (dtype == BF16 and g is not None) else "casts"
+    if route == "casts":
+        algo, out_dtype = plan.conv if plan else _CONV_ALGOS[0], torch.float32
+        pt, ptb = (plan.taps_f, plan.taps_b) if plan else (taps, taps)
     else:
-        _chk(_L().dram_pack_conv_weight(_p(w), _p(wf), _p(wb), Cout, Cin, taps, _stream()), "dram_pack_conv_weight")
+        algo, out_dtype, pt, ptb = _CONV_ALGOS[BF16], BF16, taps, taps
+        if route == "s2d":                              # stride 2: embedded weights of the stride-1 form
+            w3 = torch.empty((Cout, 8 * Cin, 3, 3, 3), device=w.device, dtype=torch.float32)
+            _chk(_L().dram_s2_embed_weight(_p(w), _p(w3), Cout, Cin, _stream()), "dram_s2_embed_weight")
+            w, Cin = w3, 8 * Cin
+    wf = torch.empty((pt, Cout, Cin), device=w.device, dtype=out_dtype) if want_fwd else None
+    wb = torch.empty((ptb, Cin, Cout), device=w.device, dtype=out_dtype) if want_bwd else None
+    ints = (Cout, Cin, taps)[:algo.pack_ints] or (plan.dref,)
+    _chk(getattr(_L(), algo.pack)(_p(w), _p(wf), _p(wb), *ints, _stream()), algo.pack)
     return wf, wb
 
 
@@ -717,6 +770,27 @@ def conv_prologue_ok(g: ConvGeom, dtype=torch.float32) -> bool:
     return dtype == torch.float32 and tuning_env("DRAM_BN_PROLOGUE", "1") != "0" and conv_plan(g).prologue
 
 
+def _launch_fwd(algo: _ConvAlgo, fn: str, lead: tuple, like: Tensor, wf: Tensor, bias: Optional[Tensor], g: ConvGeom,
+                plan: ConvPlan, rows: int, want_stats: bool, keep: bool):
+    """Allocation and launch of every forward form: `fn` is algo.fwd or one of the pipeline's forms with more input
+    operands, `lead` the pointers ahead of wf, `like` an input (device and storage type of y).  -> (y, stats, V)"""
+    y = torch.empty(g.out_shape, device=like.device, dtype=like.dtype)
+    stats = None
+    if want_stats:
+        if rows <= 0:
+            raise RuntimeError(f"dram_conv_num_mtiles rejected {g}")
+        stats = torch.empty((rows, 2, g.Cout), device=like.device, dtype=torch.float32)
+    v, tail = None, (plan.dref,)
+    if algo.ws:
+        ws = _workspace(plan.ws_fwd, like.device)
+        if keep:
+            v = torch.empty((plan.v_elems,), device=like.device, dtype=torch.float32)
+        tail = (_p(v), plan.dref, _p(ws), plan.ws_fwd)
+    with _span(algo.family, g.flops, f"fwd {g}"):
+        _chk(getattr(_L(), fn)(*lead, _p(wf), _p(bias), _p(y), _p(stats), *tail, _stream()), f"{fn}{g}")
+    return y, stats, v
+
+
 def conv3d_fwd_keep(x: Tensor, wf: Tensor, bias: Optional[Tensor], g: ConvGeom, want_stats: bool, keep: bool,
                     prologue: Optional[Tuple[Tensor, Tensor]] = None):
     """Forward conv; with keep=True on the Winograd path also returns the transformed input V
@@ -729,59 +803,41 @@ def conv3d_fwd_keep(x: Tensor, wf: Tensor, bias: Optional[Tensor], g: ConvGeom, 
     if _act(x, "x", g.in_shape):                       # bf16 storage
         if bias is not None:
             _req(bias, "bias", shape=(g.Cout,))
-        if wf.dtype == BF16 and wf.shape[2] == 8 * g.Cin:      # stride 2 as stride 1 over the space-to-depth tensor
-            return conv3d_fwd_keep(s2d(x), wf, bias, s2_geom(g), want_stats, False)
-        if wf.dtype == BF16:
-            _req(wf, "wf", BF16, (g.taps, g.Cout, g.Cin))
-            y = torch.empty(g.out_shape, device=x.device, dtype=BF16)
-            stats = torch.empty((plan.bf16_stat_rows, 2, g.Cout), device=x.device, dtype=torch.float32) if want_stats else None
-            with _span("conv3_bf16_kernel", g.flops, f"fwd {g}"):
-                _chk(_L().dram_conv3d_fwd_bf16(_p(x), _p(wf), _p(bias), _p(y), _p(stats), plan.dref, _stream()),
-                     f"dram_conv3d_fwd_bf16{g}")
-            return y, stats, None
-        # geometry outside the bf16 kernels: fp32 kernels around casts (statistics of the fp32 result)
-        y32, stats, _ = conv3d_fwd_keep(cast(x, torch.float32), wf, bias, g, want_stats, False)
-        return cast(y32, BF16), stats, None
-    algo, d = plan.algo, plan.dref
+        route, gk = bf16_route(g, plan, wf)
+        if route == "s2d":                              # stride 2 as stride 1 over the space-to-depth tensor
+            return conv3d_fwd_keep(s2d(x), wf, bias, gk, want_stats, False)
+        if route == "casts":                            # fp32 kernels around casts (statistics of the fp32 result)
+            y32, stats, _ = conv3d_fwd_keep(cast(x, torch.float32), wf, bias, g, want_stats, False)
+            return cast(y32, BF16), stats, None
+        _req(wf, "wf", BF16, (g.taps, g.Cout, g.Cin))
+        return _launch_fwd(_CONV_ALGOS[BF16], _CONV_ALGOS[BF16].fwd, (_p(x),), x, wf, bias, g, plan, plan.bf16_stat_rows,
+                           want_stats, False)
     _req(wf, "wf", shape=(plan.taps_f, g.Cout, g.Cin))
     if bias is not None:
         _req(bias, "bias", shape=(g.Cout,))
-    y = torch.empty(g.out_shape, device=x.device, dtype=torch.float32)
-    stats = None
-    if want_stats:
-        if plan.stat_rows <= 0:
-            raise RuntimeError(f"dram_conv_num_mtiles rejected {g}")
-        stats = torch.empty((plan.stat_rows, 2, g.Cout), device=x.device, dtype=torch.float32)
-    if algo == 1:
-        nbytes = plan.ws_fwd
-        ws = _workspace(nbytes, x.device)
-        v = None
-        if keep:
-            v = torch.empty((plan.v_elems,), device=x.device, dtype=torch.float32)
-        with _span("conv_wino_kernels", g.flops, f"fwd {g}"):
-            if prologue is not None:
-                _req(prologue[0], "scale", shape=(g.Cin,))
-                _req(prologue[1], "shift", shape=(g.Cin,))
-                _chk(_L().dram_wino_conv3d_fwd_bn(_p(x), _p(prologue[0]), _p(prologue[1]), _p(wf), _p(bias), _p(y), _p(stats),
-                                                  _p(v), d, _p(ws), nbytes, _stream()), f"dram_wino_conv3d_fwd_bn{g}")
-            else:
-                _chk(_L().dram_wino_conv3d_fwd(_p(x), _p(wf), _p(bias), _p(y), _p(stats), _p(v), d, _p(ws),
-                                               nbytes, _stream()), f"dram_wino_conv3d_fwd{g}")
-        return y, stats, v
-    if algo == 3:                                    # 1x1x1: plain GEMM, wf [1, Cout, Cin] is the weight itself
-        with _span("conv1x1_gemm", g.flops, f"fwd {g}"):
-            _chk(_L().dram_conv1x1_fwd(_p(x), _p(wf), _p(bias), _p(y), _p(stats), d, _stream()),
-                 f"dram_conv1x1_fwd{g}")
-        return y, stats, None
-    if algo == 2:
-        with _span("conv_wino2d_kernel", g.flops, f"fwd {g}"):
-            _chk(_L().dram_wino2d_conv3d_fwd(_p(x), _p(wf), _p(bias), _p(y), _p(stats), d, _stream()),
-                 f"dram_wino2d_conv3d_fwd{g}")
-        return y, stats, None
-    with _span("conv_igemm_kernel", g.flops, f"fwd {g}"):
-        _chk(_L().dram_conv3d_fwd(_p(x), _p(wf), _p(bias), _p(y), _p(stats), d, _stream()),
-             f"dram_conv3d_fwd{g}")
-    return y, stats, None
+    if prologue is None:
+        return _launch_fwd(plan.conv, plan.conv.fwd, (_p(x),), x, wf, bias, g, plan, plan.stat_rows, want_stats, keep)
+    _req(prologue[0], "scale", shape=(g.Cin,))
+    _req(prologue[1], "shift", shape=(g.Cin,))
+    return _launch_fwd(plan.conv, "dram_wino_conv3d_fwd_bn", (_p(x), _p(prologue[0]), _p(prologue[1])), x, wf, bias, g, plan,
+                       plan.stat_rows, want_stats, keep)
+
+
+def _launch_bwd_data(algo: _ConvAlgo, fn: str, dy: Tensor, wb: Tensor, operands: tuple, g: ConvGeom, plan: ConvPlan,
+                     overlapped: bool, detail: str, rows: int = 0):
+    """Allocation and launch of every data-gradient form: `fn` is algo.bwd or the pipeline's form that also takes the
+    BatchNorm-backward statistics (`rows` of them), `operands` the pointers behind dx.  -> (dx, partial)"""
+    dx = torch.empty(g.in_shape, device=dy.device, dtype=dy.dtype)
+    partial = torch.empty((rows, 2, g.Cin), device=dy.device, dtype=torch.float32) if rows else None
+    if partial is not None:
+        operands += (_p(partial),)
+    tail = (plan.dref,)
+    if algo.ws:                                         # (the overlapped hint is the pipeline's alone)
+        ws = _workspace(plan.ws_bwd, dy.device)
+        tail = (plan.dref_ovl if overlapped else plan.dref, _p(ws), plan.ws_bwd)
+    with _span(algo.family, g.flops, detail):
+        _chk(getattr(_L(), fn)(_p(dy), _p(wb), _p(dx), *operands, *tail, _stream()), f"{fn}{g}")
+    return dx, partial
 
 
 def conv3d_bwd_data(dy: Tensor, wb: Tensor, g: ConvGeom, add: Optional[Tensor] = None,
@@ -794,51 +850,27 @@ def conv3d_bwd_data(dy: Tensor, wb: Tensor, g: ConvGeom, add: Optional[Tensor] =
             _act(add, "add", g.in_shape, like=dy)
         if gate is not None:
             _act(gate, "gate", g.in_shape, like=dy)
-        if wb.dtype == BF16 and wb.shape[1] == 8 * g.Cin:      # stride 2: gradient of the space-to-depth tensor, then back
-            dx8 = conv3d_bwd_data(dy, wb, s2_geom(g))
+        route, gk = bf16_route(g, plan, wb, 1)
+        if route == "s2d":                              # stride 2: gradient of the space-to-depth tensor, then back
+            dx8 = conv3d_bwd_data(dy, wb, gk)
             dx = torch.empty(g.in_shape, device=dy.device, dtype=BF16)
             _chk(_L().dram_d2s_bf16(_p(dx8), _p(add), _p(gate), _p(dx), g.B, g.D, g.H, g.W, g.Cin, _stream()),
                  "dram_d2s_bf16")
             return dx
-        if wb.dtype == BF16:
-            _req(wb, "wb", BF16, (g.taps, g.Cin, g.Cout))
-            dx = torch.empty(g.in_shape, device=dy.device, dtype=BF16)
-            with _span("conv3_bf16_kernel", g.flops, f"dgrad {g}"):
-                _chk(_L().dram_conv3d_bwd_data_bf16(_p(dy), _p(wb), _p(dx), _p(add), _p(gate), plan.dref, _stream()),
-                     f"dram_conv3d_bwd_data_bf16{g}")
-            return dx
-        f32 = torch.float32
-        return cast(conv3d_bwd_data(cast(dy, f32), wb, g, None if add is None else cast(add, f32),
-                                    None if gate is None else cast(gate, f32)), BF16)
-    algo, d = plan.algo, plan.dref
-    _req(wb, "wb", shape=(plan.taps_b, g.Cin, g.Cout))
-    if add is not None:
-        _req(add, "add", shape=g.in_shape)
-    if gate is not None:
-        _req(gate, "gate", shape=g.in_shape)
-    dx = torch.empty(g.in_shape, device=dy.device, dtype=torch.float32)
-    if algo == 1:
-        nbytes = plan.ws_bwd
-        ws = _workspace(nbytes, dy.device)
-        with _span("conv_wino_kernels", g.flops, f"dgrad {g}"):
-            _chk(_L().dram_wino_conv3d_bwd_data(_p(dy), _p(wb), _p(dx), _p(add), _p(gate),
-                                                plan.dref_ovl if overlapped else d, _p(ws),
-                                                nbytes, _stream()), f"dram_wino_conv3d_bwd_data{g}")
-        return dx
-    if algo == 3:
-        with _span("conv1x1_gemm", g.flops, f"dgrad {g}"):
-            _chk(_L().dram_conv1x1_bwd_data(_p(dy), _p(wb), _p(dx), _p(add), _p(gate), d, _stream()),
-                 f"dram_conv1x1_bwd_data{g}")
-        return dx
-    if algo == 2:
-        with _span("conv_wino2d_kernel", g.flops, f"dgrad {g}"):
-            _chk(_L().dram_wino2d_conv3d_bwd_data(_p(dy), _p(wb), _p(dx), _p(add), _p(gate), d,
-                                                  _stream()), f"dram_wino2d_conv3d_bwd_data{g}")
-        return dx
-    with _span("conv_igemm_kernel", g.flops, f"dgrad {g}"):
-        _chk(_L().dram_conv3d_bwd_data(_p(dy), _p(wb), _p(dx), _p(add), _p(gate), d, _stream()),
-             f"dram_conv3d_bwd_data{g}")
-    return dx
+        if route == "casts":
+            f32 = torch.float32
+            return cast(conv3d_bwd_data(cast(dy, f32), wb, g, None if add is None else cast(add, f32),
+                                        None if gate is None else cast(gate, f32)), BF16)
+        algo = _CONV_ALGOS[BF16]
+        _req(wb, "wb", BF16, (g.taps, g.Cin, g.Cout))
+    else:
+        algo = plan.conv
+        _req(wb, "wb", shape=(plan.taps_b, g.Cin, g.Cout))
+        if add is not None:
+            _req(add, "add", shape=g.in_shape)
+        if gate is not None:
+            _req(gate, "gate", shape=g.in_shape)
+    return _launch_bwd_data(algo, algo.bwd, dy, wb, (_p(add), _p(gate)), g, plan, overlapped, f"dgrad {g}")[0]
 
 
 def conv_bwd_bnstats_ok(g: ConvGeom, dtype=torch.float32) -> bool:
@@ -862,80 +894,47 @@ def conv3d_bwd_data_bnstats(dy: Tensor, wb: Tensor, g: ConvGeom, bn_y: Tensor, m
     _req(bn_y, "bn_y", shape=g.in_shape)
     for name, t in (("mean", mean), ("invstd", invstd), ("scale", scale), ("shift", shift)):
         _req(t, name, shape=(g.Cin,))
-    rows = int(_L().dram_wino_num_stat_rows_bwd(plan.dref))
-    if rows <= 0:
+    if plan.stat_rows_bwd <= 0:
         raise RuntimeError(f"conv3d_bwd_data_bnstats: no statistic rows for {g}")
-    dx = torch.empty(g.in_shape, device=dy.device, dtype=torch.float32)
-    partial = torch.empty((rows, 2, g.Cin), device=dy.device, dtype=torch.float32)
-    nbytes = plan.ws_bwd
-    ws = _workspace(nbytes, dy.device)
-    with _span("conv_wino_kernels", g.flops, f"dgrad+bnstats {g}"):
-        _chk(_L().dram_wino_conv3d_bwd_data_bn(_p(dy), _p(wb), _p(dx), _p(bn_y), _p(mean), _p(invstd), _p(scale),
-                                               _p(shift), _p(partial), plan.dref_ovl if overlapped else plan.dref,
-                                               _p(ws), nbytes, _stream()),
-             f"dram_wino_conv3d_bwd_data_bn{g}")
-    return dx, partial
+    return _launch_bwd_data(plan.conv, "dram_wino_conv3d_bwd_data_bn", dy, wb,
+                            (_p(bn_y), _p(mean), _p(invstd), _p(scale), _p(shift)), g, plan, overlapped, f"dgrad+bnstats {g}",
+                            rows=plan.stat_rows_bwd)
 
 
 def conv3d_bwd_weight(x: Tensor, dy: Tensor, g: ConvGeom, out: Optional[Tensor] = None,
                       v_cache: Optional[Tensor] = None) -> Tensor:
     plan = conv_plan(g)
-    d, walgo = plan.dref, plan.walgo
     shape = (g.Cout, g.Cin, g.k, g.k, g.k)
     dw = out if out is not None else torch.empty(shape, device=dy.device, dtype=torch.float32)
     _req(dw, "dw", shape=shape)
     if x is not None and _act(x, "x", g.in_shape):     # bf16 storage: the gradient itself is fp32
         _act(dy, "dy", g.out_shape, like=x)
-        if plan.bf16:
-            nbytes = plan.bf16_ws_wgrad
-            ws = _workspace(nbytes, x.device)
-            with _span("wgrad3_bf16_kernel+reduce", g.flops, f"wgrad {g}"):
-                _chk(_L().dram_conv3d_bwd_weight_bf16(_p(x), _p(dy), _p(dw), d, _p(ws), nbytes, _stream()),
-                     f"dram_conv3d_bwd_weight_bf16{g}")
-            return dw
-        g8 = s2_geom(g)
-        if g8 is not None:                              # stride 2: gradient of the embedded weights, 27 of 216 slots kept
-            dw3 = conv3d_bwd_weight(s2d(x), dy, g8)
+        route, gk = bf16_route(g, plan)
+        if route == "s2d":                              # stride 2: gradient of the embedded weights, 27 of 216 slots kept
+            dw3 = conv3d_bwd_weight(s2d(x), dy, gk)
             _chk(_L().dram_s2_extract_wgrad(_p(dw3), _p(dw), g.Cout, g.Cin, _stream()), "dram_s2_extract_wgrad")
             return dw
-        return conv3d_bwd_weight(cast(x, torch.float32), cast(dy, torch.float32), g, out=dw)
-    if x is None:                                     # the forward's transformed input stands in for x (pipeline only)
-        if not (walgo == 1 and v_cache is not None and plan.ws_wgrad):
-            raise RuntimeError(f"conv3d_bwd_weight: x missing and no cached Winograd-domain input for {g}")
+        if route == "casts":
+            return conv3d_bwd_weight(cast(x, torch.float32), cast(dy, torch.float32), g, out=dw)
+        algo, nbytes = _WGRAD_ALGOS[BF16], plan.bf16_ws_wgrad
     else:
-        _req(x, "x", shape=g.in_shape)
-    _req(dy, "dy", shape=g.out_shape)
-    if walgo == 3:
-        nbytes = plan.ws_wgrad
-        ws = _workspace(max(nbytes, 4), x.device)
-        with _span("conv1x1_gemm", g.flops, f"wgrad {g}"):
-            _chk(_L().dram_conv1x1_bwd_weight(_p(x), _p(dy), _p(dw), d, _p(ws), nbytes, _stream()),
-                 f"dram_conv1x1_bwd_weight{g}")
-        return dw
-    if walgo == 2:
-        nbytes = plan.ws_wgrad
-        ws = _workspace(nbytes, x.device)
-        with _span("conv_wgrad_w2d_kernel+reduce", g.flops, f"wgrad {g}"):
-            _chk(_L().dram_wgrad_w2d(_p(x), _p(dy), _p(dw), d, _p(ws), nbytes, _stream()),
-                 f"dram_wgrad_w2d{g}")
-        return dw
-    if walgo == 1:
-        nbytes = plan.ws_wgrad
-        if nbytes:                                   # 0: this geometry's weight gradient stays on the direct path
-            ws = _workspace(nbytes, dy.device)
-            if v_cache is not None:
-                _req(v_cache, "v_cache", shape=(plan.v_elems,))
-            with _span("conv_wino_kernels", g.flops, f"wgrad {g}"):
-                _chk(_L().dram_wino_conv3d_bwd_weight(_p(x), _p(v_cache), _p(dy), _p(dw), d, _p(ws),
-                                                      nbytes, _stream()), f"dram_wino_conv3d_bwd_weight{g}")
-            return dw
-    nbytes = plan.ws_direct_wgrad
-    if nbytes == 0:
-        raise RuntimeError(f"dram_conv3d_bwd_weight: unsupported geometry {g}")
-    ws = _workspace(nbytes, x.device)
-    with _span("conv_wgrad_kernel+reduce", g.flops, f"wgrad {g}"):
-        _chk(_L().dram_conv3d_bwd_weight(_p(x), _p(dy), _p(dw), d, _p(ws), nbytes, _stream()),
-             f"dram_conv3d_bwd_weight{g}")
+        if x is None:                                   # the forward's transformed input stands in for x (pipeline only)
+            if not (plan.wgrad_from_v and v_cache is not None):
+                raise RuntimeError(f"conv3d_bwd_weight: x missing and no cached Winograd-domain input for {g}")
+        else:
+            _req(x, "x", shape=g.in_shape)
+        _req(dy, "dy", shape=g.out_shape)
+        algo, nbytes = plan.wgrad, plan.ws_wgrad
+        if nbytes == 0 and algo is _WGRAD_ALGOS[0]:
+            raise RuntimeError(f"{algo.fn}: unsupported geometry {g}")
+    ws = _workspace(max(nbytes, algo.min_ws), dy.device)
+    lead = (_p(x),)
+    if algo.v_cache:
+        if v_cache is not None:
+            _req(v_cache, "v_cache", shape=(plan.v_elems,))
+        lead = (_p(x), _p(v_cache))
+    with _span(algo.family, g.flops, f"wgrad {g}"):
+        _chk(getattr(_L(), algo.fn)(*lead, _p(dy), _p(dw), plan.dref, _p(ws), nbytes, _stream()), f"{algo.fn}{g}")
     return dw
 
 
@@ -1293,15 +1292,8 @@ def conv3d_fwd_cat(x0: Tensor, x1: Tensor, wf: Tensor, bias: Optional[Tensor], g
     _req(wf, "wf", shape=(plan.taps_f, g.Cout, g.Cin))
     if bias is not None:
         _req(bias, "bias", shape=(g.Cout,))
-    y = torch.empty(g.out_shape, device=x0.device, dtype=torch.float32)
-    stats = torch.empty((plan.stat_rows, 2, g.Cout), device=x0.device, dtype=torch.float32) if want_stats else None
-    nbytes = plan.ws_fwd
-    ws = _workspace(nbytes, x0.device)
-    v = torch.empty((plan.v_elems,), device=x0.device, dtype=torch.float32) if keep else None
-    with _span("conv_wino_kernels", g.flops, f"fwd {g}"):
-        _chk(_L().dram_wino_conv3d_fwd_cat(_p(x0), C0, _p(x1), C1, _p(wf), _p(bias), _p(y), _p(stats), _p(v), plan.dref, _p(ws),
-                                           nbytes, _stream()), f"dram_wino_conv3d_fwd_cat{g}")
-    return y, stats, v
+    return _launch_fwd(plan.conv, "dram_wino_conv3d_fwd_cat", (_p(x0), C0, _p(x1), C1), x0, wf, bias, g, plan, plan.stat_rows,
+                       want_stats, keep)
 
 
 def upcat_bwd(dcat: Tensor, src_shape, skip_shape, need_src=True, need_skip=True):
